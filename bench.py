@@ -13,17 +13,27 @@ statistics, and reduce the full state covariance from the recorded trajectories.
   --scaling strong BASELINE configs[3] / [4] as stated: --total-directions (2048) directions in
                    all, sharded over the ranks (add --segments 6 for configs[4])
 
-metric = env-steps/s over the whole job = 2 * N * H * steps / wall time of the timed region.
+metric = env-steps/s over the whole job = 2 * N * H * steps / wall time of the timed region;
+ms_per_step = that wall time / steps.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+A plain run sets up, runs W warm-up and K timed steps (no timing events inside them), and prints ONE
+JSON line on rank 0 (metric, value, unit, ms_per_step, ...).  Everything else is measured only with
+--full, which adds to the line:
   roofline      dominant kernel (rollout): algorithmic HBM bytes per launch / HIP-event
-                duration of that launch, against the 8 TB/s HBM3E peak
+                duration of that launch (events in the timed region + an untimed post-pass),
+                against the 8 TB/s HBM3E peak
   cpu_baseline  the C restatement of the reference (oracle/, OpenMP over the host cores) on
                 a bounded sample of the same workload
 and an "aux" object: the physics-step-only kernel (configs[1]) at 8192 envs and at a
-bandwidth-bound batch, the per-GPU shards of configs[3] / [4], the saturated rollout regime.
+bandwidth-bound batch, the per-GPU shards of configs[3] / [4], the saturated rollout regime
+(--no-aux / --no-cpu-baseline leave parts of it out).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns the N ranks itself)
+--dump-outputs DIR writes what the last timed step computed, as a caller of ARSAgent would receive
+it, to DIR/<name>.npy (float64): returns (the 2N rollout returns), policy, mean, covariance.  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                   (N > 1: spawns the N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (also fine)
 """
 import argparse
@@ -66,9 +76,13 @@ def parse(argv=None):
                     help="strong: ARS directions of the whole job (BASELINE configs[3]/[4])")
     ap.add_argument("--horizon", type=int, default=1000)
     ap.add_argument("--segments", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the aux legs and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's returns, policy, mean and covariance to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-aux", action="store_true")
+    ap.add_argument("--no-aux", action="store_true", help="--full: leave out the aux legs")
     ap.add_argument("--collective-one-rank-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--direct-rccl", action="store_true",
                     help="issue the all-gather straight into RCCL from native code (sw_comm) "
@@ -646,7 +660,9 @@ class ArsLeg(object):
                          safe=False, threshold=0, initial_w="Zero")
         self.agent = sw.ARSAgent(ep, ap, seed=0, device=device, full_covariance=True, direct_rccl=direct_rccl)
 
-    def run(self, warmup, steps, sync, time_every=TIME_EVERY, postpass=POSTPASS_LAUNCHES):
+    def run(self, warmup, steps, sync, time_every=TIME_EVERY, postpass=POSTPASS_LAUNCHES, after_timed=None):
+        """time_every = 0: no timing events in the timed region.  after_timed() runs right after the timed
+        steps, before the post-pass iterations move the agent on."""
         agent, torch = self.agent, self.torch
         for _ in range(warmup):
             agent.run_iteration_async(want_returns=False)
@@ -661,6 +677,8 @@ class ArsLeg(object):
         sync()
         dt = time.perf_counter() - t0
         k_ms, k_n = agent._pipe.rollout_ms()
+        if after_timed is not None:
+            after_timed()
         # post-pass outside the timed region: every launch timed, and (world > 1) the collective
         res = {"seconds": dt, "kernel_ms_timed_region": k_ms, "kernel_samples_timed_region": k_n}
         if postpass > 0 and agent.n_local > 0:
@@ -822,7 +840,7 @@ def summary(line, aux):
     def r3(x):
         return None if x is None else float(f"{x:.4g}")
 
-    roof = line["roofline"]
+    roof = line.get("roofline") or {}      # a plain run (no --full) has none
     m = f"n{dig(line, 'config', 'segments') or 3}"      # the main leg's keys carry its chain length (default 3)
     out = {m + "_ms": r3(line["ms_per_step"]), m + "_sps": r3(line["value"]), m + "_kernel_ms": r3(roof.get("kernel_ms")),
            m + "_hbm_frac": r3(roof.get("frac")), m + "_issue_frac": r3(roof.get("issue_bound_frac")),
@@ -876,6 +894,67 @@ def summary(line, aux):
         "cpu_sps": r3(dig(line, "cpu_baseline", "value")), "cpu_cores": dig(line, "cpu_baseline", "cores"),
     })
     return {k: v for k, v in out.items() if v is not None}
+
+
+def dump_outputs(agent, out_dir, rank, world):
+    """--dump-outputs: what the agent hands its caller after the last timed iteration, as out_dir/<name>.npy
+    (float64, a few KB): the 2N returns in direction order, the updated policy, the V2 running mean and the
+    state covariance.  COLLECTIVE with more than one rank (the covariance sums live on every rank); rank 0
+    writes."""
+    import numpy as np
+    from swimmer_amd.ars.sharding import returns_from_segments
+    cov = agent.reduce_covariance()
+    if rank != 0:
+        return
+    rets = returns_from_segments(agent._gathered, agent.agent_param.N, world, agent.chunk)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("returns", rets.cpu().numpy()), ("policy", agent.policy), ("mean", agent.mean),
+                    ("covariance", cov)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def main_roofline(n, H, agent, res):
+    """The main leg's `roofline` object (--full): the rollout kernel's HIP-event time against HBM and
+    against what its waves can issue, with the committed PMC traffic of the same workload."""
+    d = 2 * n + 2
+    kern_ms = res["kernel_ms"]
+    local_steps = 2 * agent.n_local * H
+    roof = leg_roofline(n, agent.n_local, H, kern_ms)
+    flops_per_step = {3: 330.0, 6: 1100.0}.get(n, 40.0 * n * n)  # fp64 flop count, DESIGN.md
+    traffic = pmc_traffic(rollout_kernel_name(n), n, agent.n_local, H)
+    cov_alg = local_steps * 8 * d       # the ride-along covariance pass reads every state once
+    stale = bool(traffic and traffic.get("stale"))
+    ib = roof.get("issue_bound") or {}
+    roof.update({
+        "traffic": (traffic or {}).get("traffic_bytes"),
+        "traffic_stale": stale,     # True: the PMC passes ran on OTHER kernel sources than this build
+        "traffic_breakdown": (traffic or {}).get("breakdown"),
+        "traffic_source": (traffic or {}).get("source"),
+        # scalars of issue_bound once more at this level (a record that keeps scalar members only
+        # still shows what bounds the kernel)
+        "issue_bound_frac": ib.get("frac"), "issue_floor_ms": ib.get("floor_ms"),
+        "instructions_per_step": ib.get("instructions_per_step"),
+        "simd_occupancy": min(1.0, -(-2 * agent.n_local // (8 if n == 3 else 4)) / 1024.0),
+        # the launch does TWO jobs: this iteration's rollouts (the bytes `achieved` counts)
+        # and the covariance pass over the previous iteration's trajectories (extra
+        # workgroups of the same grid).  Against the algorithmic bytes of both, the counters
+        # show no wasted traffic:
+        "algorithmic_bytes_with_covariance_pass": roof["algorithmic_bytes"] + cov_alg,
+        "traffic_over_algorithmic": (traffic["traffic_bytes"] / (roof["algorithmic_bytes"] + cov_alg)
+                                     if traffic and not stale else None),
+        "kernel_ms_timed_region": res["kernel_ms_timed_region"],
+        "kernel_samples_timed_region": res["kernel_samples_timed_region"],
+        "kernel_ms_postpass": res.get("kernel_ms_postpass"),
+        "kernel_samples": res["kernel_samples"],
+        "note": "the fused rollout is fp64-VALU-issue bound by construction (state, policy and "
+                "sums stay in registers; see issue_bound); HBM is the contract's roofline. "
+                "The HBM-bound regimes of this path are aux.step_only (step kernel, >= 1e6 "
+                "envs) and aux.rollout_saturated (rollouts filling the chip).  kernel_ms = "
+                "mean over the sampled launches of the timed region and every launch of an "
+                "untimed post-pass",
+        "fp64_tflops": local_steps * flops_per_step / (kern_ms * 1e-3) / 1e12,
+        "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS})
+    return roof
 
 
 def run_rank(args):
@@ -942,18 +1021,24 @@ def run_rank(args):
 
     n, H = args.segments, args.horizon
     N = args.directions * world if args.scaling == "weak" else args.total_directions
-    if rank == 0:
+    if rank == 0 and args.full:
         calibrate_issue_intervals(sw, device)
     leg = ArsLeg(sw, torch, n, H, N, device, direct_rccl=(True if args.direct_rccl else None))
     agent = leg.agent
-    res = leg.run(args.warmup, args.steps, sync)
+    # a plain run times the steps and nothing else: the kernel timing behind the roofline (HIP events in
+    # the timed region, the post-pass) is measured with --full only
+    dump = (lambda: dump_outputs(agent, args.dump_outputs, rank, world)) if args.dump_outputs else None
+    if args.full:
+        res = leg.run(args.warmup, args.steps, sync, after_timed=dump)
+    else:
+        res = leg.run(args.warmup, args.steps, sync, time_every=0, postpass=0, after_timed=dump)
     dt = max_over_ranks(res["seconds"])
     if world > 1:
         same_policy_everywhere(agent, "timed")
     leg.check(rank)
 
     strong = None
-    if world > 1 and args.scaling == "weak" and not args.no_aux:
+    if args.full and world > 1 and args.scaling == "weak" and not args.no_aux:
         # the fixed-size problem of configs[3] / [4] on the same ranks (strong scaling), so one
         # driver run per N yields both curves
         sleg = ArsLeg(sw, torch, n, H, args.total_directions, device)
@@ -970,45 +1055,8 @@ def run_rank(args):
     if rank == 0:
         steps_per_iter = 2 * N * H
         value = steps_per_iter * args.steps / dt
-        d = 2 * n + 2
-        kern_ms = res["kernel_ms"]
-        assert res["kernel_samples_timed_region"] == -(-args.steps // TIME_EVERY)
-        local_steps = 2 * agent.n_local * H
-        roof = leg_roofline(n, agent.n_local, H, kern_ms)
-        flops_per_step = {3: 330.0, 6: 1100.0}.get(n, 40.0 * n * n)  # fp64 flop count, DESIGN.md
-        traffic = pmc_traffic(rollout_kernel_name(n), n, agent.n_local, H)
-        cov_alg = local_steps * 8 * d       # the ride-along covariance pass reads every state once
-        stale = bool(traffic and traffic.get("stale"))
-        ib = roof.get("issue_bound") or {}
-        roof.update({
-            "traffic": (traffic or {}).get("traffic_bytes"),
-            "traffic_stale": stale,     # True: the PMC passes ran on OTHER kernel sources than this build
-            "traffic_breakdown": (traffic or {}).get("breakdown"),
-            "traffic_source": (traffic or {}).get("source"),
-            # scalars of issue_bound once more at this level (a record that keeps scalar members only
-            # still shows what bounds the kernel)
-            "issue_bound_frac": ib.get("frac"), "issue_floor_ms": ib.get("floor_ms"),
-            "instructions_per_step": ib.get("instructions_per_step"),
-            "simd_occupancy": min(1.0, -(-2 * agent.n_local // (8 if n == 3 else 4)) / 1024.0),
-            # the launch does TWO jobs: this iteration's rollouts (the bytes `achieved` counts)
-            # and the covariance pass over the previous iteration's trajectories (extra
-            # workgroups of the same grid).  Against the algorithmic bytes of both, the counters
-            # show no wasted traffic:
-            "algorithmic_bytes_with_covariance_pass": roof["algorithmic_bytes"] + cov_alg,
-            "traffic_over_algorithmic": (traffic["traffic_bytes"] / (roof["algorithmic_bytes"] + cov_alg)
-                                         if traffic and not stale else None),
-            "kernel_ms_timed_region": res["kernel_ms_timed_region"],
-            "kernel_samples_timed_region": res["kernel_samples_timed_region"],
-            "kernel_ms_postpass": res.get("kernel_ms_postpass"),
-            "kernel_samples": res["kernel_samples"],
-            "note": "the fused rollout is fp64-VALU-issue bound by construction (state, policy and "
-                    "sums stay in registers; see issue_bound); HBM is the contract's roofline. "
-                    "The HBM-bound regimes of this path are aux.step_only (step kernel, >= 1e6 "
-                    "envs) and aux.rollout_saturated (rollouts filling the chip).  kernel_ms = "
-                    "mean over the sampled launches of the timed region and every launch of an "
-                    "untimed post-pass",
-            "fp64_tflops": local_steps * flops_per_step / (kern_ms * 1e-3) / 1e12,
-            "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS})
+        if args.full:
+            assert res["kernel_samples_timed_region"] == -(-args.steps // TIME_EVERY)
         if args.scaling == "weak":
             workload = (f"ARS V2 iteration, {n}-segment swimmer, {args.directions} directions/GPU x 2 "
                         f"rollouts x H={H} (BASELINE configs[2] per GPU)")
@@ -1027,10 +1075,11 @@ def run_rank(args):
                                       "1 all-gather/iteration",
                        "ranks_seen": dist.get_world_size() if world > 1 else 1,
                        "backend": (dist.get_backend() if world > 1 else None)},
-            "roofline": roof,
         }
+        if args.full:
+            line["roofline"] = main_roofline(n, H, agent, res)
         aux = {}
-        if world > 1:
+        if args.full and world > 1:
             aux["collective_us"] = res.get("collective_us")
             if strong:
                 aux["strong_2048_directions"] = strong
@@ -1042,7 +1091,7 @@ def run_rank(args):
             except Exception as exc:   # noqa: BLE001 -- reported in the line
                 return {"error": f"{type(exc).__name__}: {exc}"}
 
-        if not args.no_aux and world == 1:
+        if args.full and not args.no_aux and world == 1:
             aux["step_only"] = guarded(aux_step_only, sw, torch, n, device)
             # configs[3]'s whole problem on ONE GPU
             aux["ars_2048_directions_one_gpu"] = guarded(aux_ars_shard, sw, torch, n, H, 2048, device,
@@ -1073,11 +1122,11 @@ def run_rank(args):
             # H = 500 keeps the buffer at 3.7 GB): where the lane kernel's O(n^2 .. n^3) step stands against HBM
             aux["rollout_saturated_n6"] = guarded(aux_rollout_saturated, sw, torch, device, n=6, n_roll=65536,
                                                   H=500, reps=9)
-        if not args.no_aux and world == 1:
+        if args.full and not args.no_aux and world == 1:
             aux["single_env"] = guarded(aux_single_env, sw, torch, device)
         if aux:
             line["aux"] = aux
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = guarded(cpu_baseline, n, H, args.directions, args.cpu_seconds)
         # LAST key, flat and short (< 1900 characters): every config's number survives a record
         # that keeps only the tail of the line and only scalar members of its objects

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """profiles/rNN_pmc_traffic.json from the two rocprofv3 PMC passes of the bench command.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR_F -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-aux
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d DIR_F -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-aux
     rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d DIR_W -- python3 bench.py ... (same)
     python scripts/pmc_traffic_json.py FETCH.csv WRITE.csv profiles/r03_pmc_traffic.json
 

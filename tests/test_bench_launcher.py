@@ -29,6 +29,9 @@ def test_flags_of_both_scaling_modes():
     assert (a.scaling, a.directions, a.total_directions, a.segments) == ("weak", 512, 2048, 3)
     a = bench.parse(["--gpus", "8", "--scaling", "strong", "--segments", "6"])
     assert (a.scaling, a.total_directions, a.segments) == ("strong", 2048, 6)
+    assert (a.full, a.dump_outputs) == (False, None)                        # a plain run times the steps only
+    a = bench.parse(["--steps", "7", "--full", "--dump-outputs", "out"])
+    assert (a.steps, a.full, a.dump_outputs) == (7, True, "out")
 
 
 RANK_SCRIPT = textwrap.dedent("""

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -29,13 +30,18 @@ def _rehearse(*flags):
 
 def test_strong_scaling_of_the_six_segment_config_on_four_ranks():
     """configs[4] as `bench.py --gpus N --scaling strong --segments 6` runs it: 2048 directions in all."""
-    rec = _rehearse("--scaling", "strong", "--segments", "6")
+    rec = _rehearse("--scaling", "strong", "--segments", "6", "--full")      # + the timed post-pass over the ranks
     assert rec["n_gpus"] == 4 and rec["scaling"] == "strong" and rec["config"]["ranks_seen"] == 4
+    assert rec["roofline"]["kernel_samples"] > 0
     assert rec["config"]["segments"] == 6 and rec["config"]["directions_total"] == 2048
     assert rec["value"] > 0 and rec["steps"] == 3
 
 
-def test_weak_scaling_on_four_ranks():
-    rec = _rehearse()
+def test_weak_scaling_on_four_ranks(tmp_path):
+    rec = _rehearse("--dump-outputs", str(tmp_path))      # the dump is collective: every rank's covariance sums
     assert rec["n_gpus"] == 4 and rec["scaling"] == "weak" and rec["config"]["ranks_seen"] == 4
+    assert "roofline" not in rec and rec["value"] > 0 and rec["steps"] == 3
     assert rec["config"]["directions_total"] == 4 * 512
+    rets, cov = np.load(tmp_path / "returns.npy"), np.load(tmp_path / "covariance.npy")
+    assert rets.shape == (2 * 4 * 512,) and np.isfinite(rets).all() and np.unique(rets).size > 512
+    assert cov.shape == (8, 8) and np.isfinite(cov).all() and np.allclose(cov, cov.T)
