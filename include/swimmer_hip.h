@@ -16,6 +16,9 @@
  *   sw_rollout_f64       Environment.select_action + .rollout       ars/environment.py:19-57
  *   sw_ars_rollouts_f64  ARSAgent.runOneIteration's perturb + 2N rollouts loop
  *                                                                   ars/ars_agent.py:137-172
+ *   sw_ars_gate_f64      ARSAgent.runOneIteration's simulator gate (safe=True): both simulator
+ *                        rollouts of every direction + the admit decision
+ *                                                                   ars/ars_agent.py:144-157
  *   sw_ars_update_f64    ARSAgent.sort_directions / update_policy and the V2 statistics
  *                                                                   ars/ars_agent.py:97-130, :176-182
  *   sw_traj_moments_f64  np.mean / np.cov over the saved states     ars/ars_agent.py:180-182
@@ -175,6 +178,22 @@ int sw_ars_rollouts_f64(const sw_params *p, int64_t dir_begin, int64_t n_dir, in
                         const double *policy, const double *deltas, double nu,
                         const double *mean, const double *inv_std, double *returns,
                         double *traj, double *moments, int32_t *status, void *stream);
+
+/* The safe-ARS simulator gate (ars_agent.py:144-157).  For directions i in [dir_begin, dir_begin + n_dir)
+ * run the rollouts P + nu*delta_i and P - nu*delta_i in the simulator `sim` from the reset state, whitened
+ * with mean / inv_std exactly as sw_ars_rollouts_f64 does (both NULL for V1), and decide in the same launch
+ *   admit[j] = !(r_j+ <= sim_thresh) && !(r_j- <= sim_thresh)        (j = i - dir_begin)
+ * the reference's rule: a return equal to the threshold refuses; a NaN return or a NaN threshold admits
+ * (x <= NaN is false and the reference then takes the real rollout).  Computing r_j- also when r_j+
+ * already refuses is equivalent: the reference's skipped rollout has no side effect.
+ * Stores no trajectories and no moments.  The kernel form is the one sw_ars_rollouts_f64 picks without
+ * trajectories (mirror-quad / quad for n = 3, row for n = 4..8, lane otherwise; SW_FLAG_ROLLOUT_* honoured).
+ *   admit   : [n_dir], required          returns : NULL or [2 * n_dir], as sw_ars_rollouts_f64's
+ *   status  : NULL or [2 * n_dir], as sw_ars_rollouts_f64's */
+int sw_ars_gate_f64(const sw_params *sim, int64_t dir_begin, int64_t n_dir, int32_t H,
+                    const double *policy, const double *deltas, double nu,
+                    const double *mean, const double *inv_std, double sim_thresh,
+                    int32_t *admit, double *returns, int32_t *status, void *stream);
 
 /* ARS policy update + V2 statistics.
  *   returns       : [2 * n_dir] all returns of the iteration (after the all-gather)

@@ -10,7 +10,8 @@ SOURCES = ["swimmer_kernels.hip", "host_rng.cpp", "direct_comm.cpp"]
 HOST_ONLY = {"host_rng.cpp"}   # plain C++, no device pass: it picks its vector width from the CPU's features at
                                # run time (x86 builtins the device pass of a HIP compile refuses)
 HEADERS = ["rlglue_env.cpp", os.path.join("..", "..", "include", "rlglue_swimmer.h"),
-           "swimmer_device.h", "swimmer_quad3.h", "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h", os.path.join("..", "..", "include", "swimmer_hip.h")]
+           "swimmer_device.h", "swimmer_rollout_lane.inc", "swimmer_rollout_quad3.inc",
+           "swimmer_rollout_oct3.inc", "swimmer_rollout_row.inc", "swimmer_quad3.h", "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h", os.path.join("..", "..", "include", "swimmer_hip.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC"] + os.environ.get("SWIMMER_HIPCC_EXTRA", "").split()
 LINK_LIBS = ["-ldl"]   # direct_comm.cpp resolves RCCL at run time
 

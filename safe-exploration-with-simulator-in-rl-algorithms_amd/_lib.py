@@ -81,6 +81,9 @@ _PROTOTYPES = {
     "sw_ars_rollouts_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_double] + [ctypes.c_void_p] * 7),
+    "sw_ars_gate_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_double] + [ctypes.c_void_p] * 4),
     "sw_ars_update_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_int64, ctypes.c_void_p,

@@ -17,8 +17,23 @@ drawn as 2*rand(m, d)-1, ars_agent.py:95,137).  What differs is where the work h
     the sums of its own shard: `reduce_covariance()` is the (explicit) collective that adds
     them up; the `covariance` attribute itself never communicates.
 
-The safe-exploration gate (ars_agent.py:144-157) is sequential by construction and is not
-part of this path: agent_param.safe=True raises NotImplementedError.
+Safe exploration (agent_param.safe=True, ars_agent.py:40-66, :144-157): before any real rollout,
+both rollouts P +- nu*delta_i of every direction run in a SIMULATOR built from the estimated
+parameters, and the direction is admitted only if neither simulator return is <= sim_threshold.
+Within an iteration the gate of direction i depends on the policy, delta_i, the frozen V2
+statistics and the estimated parameters only, so the 2N simulator rollouts are ONE launch of
+sw_ars_gate_f64 (returns only, the decision fused into the kernel).  The admit flags are the ONE
+device->host read the safe path adds per iteration; the admitted deltas, packed in ascending
+direction order, then go through the same pipeline as above with n_dir = k (k = admitted count),
+and nothing is enqueued when k = 0.  Deviation where the reference has no answer: with N > 1 and
+some but not all directions refused, the reference's sort_directions indexes rewards[2*i] for
+every i < N and raises IndexError (ars_agent.py:105); here only the k admitted directions are
+ranked and used, each with its own delta, sigma_R is taken over their 2k returns, the step is
+divided by agent_param.b as in the reference, and top_b is clamped to k.  For N = 1, and for
+iterations where all or none of the directions pass, this is the reference's behaviour.  Argument
+errors the reference only meets later are raised at construction: sim_thresh=None and a missing
+data_path raise ValueError; the gate is not sharded, so more than one rank raises
+NotImplementedError.
 
 Streams: every launch goes to torch's CURRENT stream.  With a NCCL process group alive, work on
 the null (default) stream is implicitly ordered against the group's streams, which costs an
@@ -41,21 +56,46 @@ from .sharding import (all_gather_segments, returns_from_segments, segment_len,
                        shard_bounds)
 
 
+def approximate_env_param(env_param, approx_error):
+    """The reference's approximation branch (ars_agent.py:45-53): a direction drawn from NumPy's
+    global generator (rand(3), normalised) scaled by approx_error, added to m_i, l_i, k.  Like the
+    reference it MUTATES and returns `env_param` itself (renamed 'LeonSwimmer-Simulator')."""
+    unknowns = ('m_i', 'l_i', 'k')
+    delta = np.random.rand(len(unknowns))
+    delta = delta / np.linalg.norm(delta, ord=2) * approx_error
+    env_param.name = 'LeonSwimmer-Simulator'
+    env_param.m_i += delta[0]
+    env_param.l_i += delta[1]
+    env_param.k += delta[2]
+    return env_param
+
+
+def simulator_threshold(agent_param, real_env_param, sim_thresh):
+    """threshold + alpha(H) * epsilon (ars_agent.py:59-63)."""
+    alpha = sim_thresh.compute_alpha(agent_param.H)
+    return agent_param.threshold + alpha * real_env_param.epsilon
+
+
 class ARSAgent(object):
 
     def __init__(self, real_env_param, agent_param, data_path=None, seed=None,
                  guess_param=None, approx_error=None, sim_thresh=None, *, device=None,
                  process_group=None, record_trajectories=False, full_covariance=True,
                  top_b=0, rollout_kernel="auto", direct_rccl=None):
-        if agent_param.safe:
-            raise NotImplementedError(
-                "safe exploration (ars_agent.py:144-157) gates every real rollout on a "
-                "simulator rollout, one at a time; it is outside the data-parallel path")
-        require_gpu()
+        self.safe = bool(agent_param.safe)
+        if self.safe:
+            # the reference reaches `...` (ars_agent.py:64-65) / np.load(None) and fails later
+            if sim_thresh is None:
+                raise ValueError("safe=True needs sim_thresh (a Threshold) to set the simulator threshold")
+            if data_path is None:
+                raise ValueError("safe=True needs data_path: the real-world trajectories the agent loads")
         self.distributed = dist.is_available() and dist.is_initialized()
         self.group = process_group
         self.world = dist.get_world_size(process_group) if self.distributed else 1
         self.rank = dist.get_rank(process_group) if self.distributed else 0
+        if self.safe and self.world > 1:
+            raise NotImplementedError("safe=True runs on one rank: the simulator gate is not sharded")
+        require_gpu()
         if device is None:
             device = f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}"
         self.device = torch.device(device)
@@ -74,6 +114,31 @@ class ARSAgent(object):
         self.params = SwParams.make(n, real_env_param.l_i, real_env_param.m_i,
                                     real_env_param.k, real_env_param.h, (1.0, 0.0),
                                     flags=kernel_flags(rollout_kernel))
+        # Safe exploration (ars_agent.py:40-66).  self.params above holds the real world's values
+        # from BEFORE the approximation branch mutates real_env_param, as the reference's real_world
+        # env was built before it.
+        self.violations = 0                            # real returns below threshold so far
+        self.last_admitted = np.zeros(0, dtype=np.int64)
+        self.estimated_param = self.sim_threshold = self.p_sim = None
+        if self.safe:
+            self.database.load(data_path)
+            if guess_param is not None:
+                from .estimator import Estimator    # needs the optional `cma` (ImportError without it)
+                print("Using computed estimation...")
+                self.estimated_param = Estimator(self.database, guess_param,
+                                                 capacity=1).estimate_real_env_param()
+            elif approx_error is not None:
+                print("Using approximated estimation...")
+                self.estimated_param = approximate_env_param(real_env_param, approx_error)
+            else:
+                print("Using exact estimation...")
+                self.estimated_param = real_env_param
+            print(f"Used estimation: {self.estimated_param}")
+            self.sim_threshold = simulator_threshold(agent_param, real_env_param, sim_thresh)
+            print(f"Simulator threshold is {self.sim_threshold}")
+            est = self.estimated_param
+            self.p_sim = SwParams.make(est.n, est.l_i, est.m_i, est.k, est.h, (1.0, 0.0),
+                                       flags=kernel_flags(rollout_kernel))
         if agent_param.initial_w == 'Zero':
             policy = np.zeros((self.m, self.d))
         else:
@@ -95,8 +160,12 @@ class ARSAgent(object):
         self.n_local = self.hi - self.lo
         # covariance sums of this rank's shard [count | sum x | sum x x^T] + the pass's scratch
         self._cov_sums = 1 + self.d + self.d * self.d
-        self._cov_acc = (kernels.new_cov_acc(self.params, 2 * self.n_local, H, self.device)
-                         if self.full_covariance else None)
+        cov_doubles = kernels.cov_acc_doubles(self.params, 2 * self.n_local, H)
+        if self.safe:
+            # a safe iteration's pass covers the 2k admitted rollouts; the scratch a pass needs is
+            # not monotone in the rollout count, so size it for every k <= N
+            cov_doubles = max(kernels.cov_acc_doubles(self.params, 2 * k, H) for k in range(1, N + 1))
+        self._cov_acc = (torch.zeros(cov_doubles, **f64) if self.full_covariance else None)
         self._coll_events = None
         self._cov_total = None       # all ranks' sums as of iteration _cov_total_it (world > 1)
         self._cov_total_it = -1
@@ -134,6 +203,11 @@ class ARSAgent(object):
         self._traj = self._traj2[0]
         self._status = torch.zeros(max(1, 2 * self.n_local), dtype=torch.int32,
                                    device=self.device)
+        if self.safe:
+            self._gate_deltas = torch.empty((N, self.m, self.d), **f64)
+            self._gate_returns = torch.empty(2 * N, **f64)
+            # [admit (N) | simulator status (2N)]: read back with ONE device->host copy
+            self._gate_flags = torch.zeros(3 * N, dtype=torch.int32, device=self.device)
 
         # The exchange: torch.distributed (default), or -- direct_rccl=True / SWIMMER_DIRECT_RCCL=1 --
         # ncclAllGather called from native code on the critical stream with a communicator of this
@@ -278,6 +352,8 @@ class ARSAgent(object):
         """One ARS iteration without synchronising the host; returns the [2N] returns as a
         device tensor (a view of the result segment, valid until the next iteration), or
         None with want_returns=False."""
+        if self.safe:
+            return self._run_safe_iteration(deltas, want_returns)
         ap = self.agent_param
         i = self._pipe.next_slot()               # the pipeline's own count, not self._it
         self._it += 1
@@ -318,6 +394,72 @@ class ARSAgent(object):
         if not want_returns:
             return None
         return returns_from_segments(gathered, ap.N, self.world, self.chunk)
+
+    def _run_safe_iteration(self, deltas=None, want_returns=True):
+        """One safe iteration (ars_agent.py:137-184): the gate launch over all N directions, ONE
+        device->host read of its admit flags and simulator status codes (a failed simulator rollout raises
+        LinAlgError, as a failed real rollout does), then the pipeline's real rollouts and update over the
+        k admitted directions (packed in ascending order; none enqueued when k = 0).  Returns the
+        2k real returns as a device tensor (a view of the result segment), or None."""
+        ap = self.agent_param
+        N, H = ap.N, ap.H
+        i = self._pipe.next_slot()
+        self._it += 1
+        self._pipe.host_slot_wait(i)
+        host = self._deltas_host_np[i]
+        if deltas is None:      # the same draws as sample_deltas()
+            numpy_global_uniform_pm1(host)
+        else:
+            host[...] = deltas
+        self._gate_deltas.copy_(self._deltas_host[i], non_blocking=True)
+        kernels.ars_gate(self.p_sim, H, self._policy, self._gate_deltas, ap.nu, 0, N, self.sim_threshold,
+                         self._mean, self._inv_std, returns=self._gate_returns,
+                         status=self._gate_flags[N:], admit=self._gate_flags[:N])
+        flags = self._gate_flags.cpu().numpy()               # the one added device->host read
+        if np.any(flags[N:] != 0):
+            # a failed simulator rollout returns NaN, and NaN would admit its direction unnoticed
+            raise np.linalg.LinAlgError("Singular matrix / non-finite state in a simulator rollout of the gate")
+        admitted = np.flatnonzero(flags[:N])
+        k = len(admitted)
+        self.last_admitted = admitted
+        if k == 0:
+            return self._send[:0] if want_returns else None
+        if self.record_trajectories:
+            self._policy_snapshot = self._policy.cpu().numpy()
+        if k < N:
+            host[:k] = host[admitted]
+        n_roll, width = 2 * k, 2 * self.d
+        self._deltas = self._deltas2[i]
+        traj = self._traj2[i]
+        if traj is not None:    # [H, d, 2k] at the start of the [H, d, 2N] buffer
+            traj = traj.view(-1)[:H * self.d * n_roll].view(H, self.d, n_roll)
+        self._traj = traj
+        moments = None
+        if self.v2:
+            rows, base = kernels.moments_blocks(n_roll), 2 * self.chunk
+            moments = self._send[base:base + rows * width].view(rows, width)
+            # the update sums all rows_chunk rows of the segment: the unused ones must add nothing
+            self._send[base + rows * width:base + self.rows_chunk * width].zero_()
+        self._pipe.rollouts(i, self.params, k, 0, k, H, self._deltas_host[i], self._deltas,
+                            self._policy, ap.nu, self._mean, self._inv_std, self._send[:n_roll],
+                            traj, moments, self._cov_acc if traj is not None else None,
+                            self._status[:n_roll])
+        gathered = self._exchange()
+        n_new = 2 * k * H
+        self._pipe.update(i, self.params, k, gathered, self.world, self.chunk, self.rows_chunk,
+                          self._deltas, self._policy, ap.alpha, ap.b, min(self.top_b, k),
+                          self._running, n_new, self._mean, self._inv_std, self._sigma)
+        if self.v2:
+            self.n_saved_states += n_new
+        if self.record_trajectories and traj is not None:
+            P, nd = self._policy_snapshot, ap.nu * host[:k]
+            pols = np.empty((n_roll, self.m, self.d))
+            pols[0::2] = P + nd
+            pols[1::2] = P - nd
+            self.database.add_device_batch(traj.clone(), pols)
+        if not want_returns:
+            return None
+        return returns_from_segments(gathered, k, self.world, self.chunk)
 
     def _rollout_policies(self, deltas):
         """Host copy of the 2*n_local perturbed policies of this rank's shard, in rollout
@@ -412,11 +554,20 @@ class ARSAgent(object):
         torch.cuda.synchronize(self.device)
 
     def runOneIteration(self):
-        """One whole ARS iteration (ars_agent.py:132-185); returns the list of 2N returns."""
+        """One whole ARS iteration (ars_agent.py:132-185); returns the list of 2N returns
+        (safe=True: the 2k returns of the admitted directions' real rollouts, in order)."""
         rets = self.run_iteration_async()
         out = rets.cpu().numpy()
-        if int((self._status != 0).sum().item()):
+        status = self._status[:out.size] if self.safe else self._status
+        if int((status != 0).sum().item()):
             raise np.linalg.LinAlgError("Singular matrix / non-finite state in a rollout")
+        if self.safe:
+            threshold = self.agent_param.threshold
+            for reward in out:
+                if reward < threshold:
+                    print(f"Obtained in real world rollout a return of {reward}, below the "
+                          f"threshold {threshold}")
+                    self.violations += 1
         return out.tolist()
 
     def runTraining(self, save_data_path=None, save_policy_path=None):

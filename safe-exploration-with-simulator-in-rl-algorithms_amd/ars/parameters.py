@@ -21,7 +21,7 @@ bare dataclasses they validate what the GPU path relies on.
         N         exploration directions per iteration
         b         divisor of the update step (the reference never truncates to the top b)
         alpha,nu  step size, exploration noise scale
-        safe, threshold   safe-exploration gate (sequential by construction: not on this path)
+        safe, threshold   safe-exploration gate: simulator-gated real rollouts (ARSAgent, sw_ars_gate_f64)
         initial_w 'Zero' or the path of a .npy policy
 """
 from dataclasses import dataclass

@@ -383,6 +383,37 @@ env1_kernel(sw::Consts C, sw::TwinConsts T, double *__restrict__ io, int32_t *__
 }
 
 // ------------------------------------------------------------------------------------
+// The ARS simulator gate (sw_ars_gate_f64, ars_agent.py:146-157): direction i is admitted unless one of
+// its two simulator returns is <= the threshold.  `x <= thr` is false for a NaN on either side, so a
+// NaN return or a NaN threshold admits, as in the reference.  Rollouts 2i and 2i + 1 of a direction
+// sit in one wave in every kernel form, XOR lanes apart: one ds_swizzle (bit-mask mode, XOR < 32)
+// hands each owner lane its partner's return, the even rollout's owner stores the flag.  Every lane
+// of the pair's owners must be active (both rollouts of a direction are valid or neither is).
+template <int XOR>
+__device__ __forceinline__ double swizzle_xor_f64(double v)
+{
+    static_assert(XOR > 0 && XOR < 32, "ds_swizzle bit-mask mode reaches lanes within 32");
+    constexpr int kPattern = 0x1f | (XOR << 10);   // and_mask 0x1f, or_mask 0, xor_mask XOR
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_ds_swizzle(lo, kPattern);
+    hi = __builtin_amdgcn_ds_swizzle(hi, kPattern);
+    return __hiloint2double(hi, lo);
+}
+
+template <int XOR>
+__device__ __forceinline__ void gate_store(double ret, int code, bool owner, int64_t r, double thr,
+                                           double *__restrict__ returns, int32_t *__restrict__ status,
+                                           int32_t *__restrict__ admit)
+{
+    const double partner = swizzle_xor_f64<XOR>(ret);
+    if (owner) {
+        if (returns) returns[r] = ret;
+        if (status) status[r] = code;
+        if ((r & 1) == 0) admit[r >> 1] = (!(ret <= thr) && !(partner <= thr)) ? 1 : 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Rollouts.  ARS = false: policies[r][m][d] given per rollout.  ARS = true: rollout r is
 // direction dir_begin + (r >> 1) with sign + (r even) / - (r odd); its policy
 // P +- nu * delta is built here (ars_agent.py:141-142), so the perturbed policies never
@@ -397,168 +428,29 @@ rollout_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H, const 
                double *__restrict__ traj, double *__restrict__ final_state,
                double *__restrict__ moments, int32_t *__restrict__ status)
 {
-    constexpr int D = 2 * N + 2, M = N - 1;
-    const int64_t r = (int64_t)blockIdx.x * kRollBlock + threadIdx.x;
-    const bool active = r < n_roll;
-    const bool v2 = (mean != nullptr);
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
 
-    double m1[D], m2[D];  // V2 moment sums of (s - c), c = reset state
-#pragma unroll
-    for (int j = 0; j < D; ++j) m1[j] = m2[j] = 0.0;
-
-    if (active) {
-        // ---- policy into registers ----
-        double W[M][D];
-        if (ARS) {
-            const int64_t dir = dir_begin + (r >> 1);
-            const double sgn = (r & 1) ? -1.0 : 1.0;
-            const double *dl = deltas + dir * (M * D);
-#pragma unroll
-            for (int i = 0; i < M; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    const double t = __dmul_rn(nu, dl[i * D + j]);
-                    W[i][j] = __dadd_rn(policies[i * D + j], sgn * t);
-                }
-        } else {
-            const double *pl = policies + r * (M * D);
-#pragma unroll
-            for (int i = 0; i < M; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) W[i][j] = pl[i * D + j];
-        }
-        if (v2) {
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const double sc = inv_std[j];
-#pragma unroll
-                for (int i = 0; i < M; ++i) W[i][j] = __dmul_rn(W[i][j], sc);
-            }
-        }
-        // action = W (s - mu) = W s - W mu: the constant part once per rollout
-        double nbias[M];
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            nbias[i] = 0.0;
-            if (v2) {
-#pragma unroll
-                for (int j = 0; j < D; ++j) nbias[i] = __builtin_fma(-W[i][j], mean[j], nbias[i]);
-            }
-        }
-
-        // ---- start state ----
-        double gdx, gdy, th[N], thd[N];
-        if (state0) {
-            gdx = state0[r];
-            gdy = state0[n_roll + r];
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                th[i] = state0[(int64_t)(2 + 2 * i) * n_roll + r];
-                thd[i] = state0[(int64_t)(3 + 2 * i) * n_roll + r];
-            }
-        } else {
-            gdx = gdy = TWIN ? kTwinStart : 0.0;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                th[i] = TWIN ? kTwinStart : kHalfPi;
-                thd[i] = TWIN ? kTwinStart : 0.0;
-            }
-        }
-
-        double total = 0.0;
-        bool ok = true;
-        double thmax = 0.0;  // largest |theta| fed to sincos_fast
-        for (int32_t t = 0; t < H; ++t) {
-            thmax = sw::track_angle_range<N>(thmax, th);
-            // action = W (s - mu)   (ars/environment.py:29 / :34); two partial sums
-            double sm[D];
-            sm[0] = gdx;
-            sm[1] = gdy;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                sm[2 + 2 * i] = th[i];
-                sm[3 + 2 * i] = thd[i];
-            }
-            double u[M];
-#pragma unroll
-            for (int i = 0; i < M; ++i) {
-                double a0 = __builtin_fma(W[i][0], sm[0], nbias[i]), a1 = W[i][1] * sm[1];
-#pragma unroll
-                for (int j = 2; j < D; j += 2) {
-                    a0 = __builtin_fma(W[i][j], sm[j], a0);
-                    a1 = __builtin_fma(W[i][j + 1], sm[j + 1], a1);
-                }
-                u[i] = a0 + a1;
-            }
-            double rew;
-            ok = (TWIN ? sw::twin_step<N>(T, gdx, gdy, th, thd, u, rew)
-                       : sw::euler_step<N>(C, gdx, gdy, th, thd, u, rew)) && ok;
-            total += rew;
-            if (traj) {
-                double *tp = traj + (int64_t)t * D * n_roll + r;
-                tp[0] = gdx;
-                tp[n_roll] = gdy;
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-                    tp[(int64_t)(2 + 2 * i) * n_roll] = th[i];
-                    tp[(int64_t)(3 + 2 * i) * n_roll] = thd[i];
-                }
-            }
-            if (moments) {
-                m1[0] += gdx;
-                m2[0] = __builtin_fma(gdx, gdx, m2[0]);
-                m1[1] += gdy;
-                m2[1] = __builtin_fma(gdy, gdy, m2[1]);
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-                    const double a = th[i] - kHalfPi;
-                    m1[2 + 2 * i] += a;
-                    m2[2 + 2 * i] = __builtin_fma(a, a, m2[2 + 2 * i]);
-                    m1[3 + 2 * i] += thd[i];
-                    m2[3 + 2 * i] = __builtin_fma(thd[i], thd[i], m2[3 + 2 * i]);
-                }
-            }
-        }
-        bool fin = isfinite(gdx) && isfinite(gdy);
-#pragma unroll
-        for (int i = 0; i < N; ++i) fin = fin && isfinite(th[i]) && isfinite(thd[i]);
-        const bool in_range = thmax < sw::kAngleLimit;
-        // an angle outside sincos_fast's range makes every later number meaningless: fail
-        // loudly (NaN return + status bit) instead of returning finite garbage
-        returns[r] = in_range ? total : __builtin_nan("");
-        if (status)
-            status[r] = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) |
-                        (in_range ? 0 : SW_STATUS_RANGE);
-        if (final_state) {
-            final_state[r] = gdx;
-            final_state[n_roll + r] = gdy;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                final_state[(int64_t)(2 + 2 * i) * n_roll + r] = th[i];
-                final_state[(int64_t)(3 + 2 * i) * n_roll + r] = thd[i];
-            }
-        }
-    }
-
-    if (moments) {
-        // fixed-order butterfly over each group of 16 lanes (deterministic); one row of
-        // partial sums per 16 rollouts, the same partition the quad kernel produces
-        const int64_t n_rows = (n_roll + kMomGroup - 1) / kMomGroup;
-        const int64_t row = (int64_t)blockIdx.x * (kRollBlock / kMomGroup) + threadIdx.x / kMomGroup;
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            double a = m1[j], b = m2[j];
-#pragma unroll
-            for (int off = kMomGroup / 2; off > 0; off >>= 1) {
-                a += __shfl_down(a, off, kMomGroup);
-                b += __shfl_down(b, off, kMomGroup);
-            }
-            if (threadIdx.x % kMomGroup == 0 && row < n_rows) {
-                moments[row * (2 * D) + j] = a;
-                moments[row * (2 * D) + D + j] = b;
-            }
-        }
-    }
+// The ARS simulator gate (sw_ars_gate_f64) in the lane form: one rollout per lane, any n, either model.
+// The body is rollout_kernel's (swimmer_rollout_lane.inc) with ARS on, no trajectories / final state /
+// moments, and the decision (gate_store) in place of the plain return store.
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                const double *__restrict__ mean, const double *__restrict__ inv_std, double gate_thr,
+                int32_t *__restrict__ admit, double *__restrict__ returns, int32_t *__restrict__ status)
+{
+    constexpr bool ARS = true;
+    const double *const state0 = nullptr;
+    double *const traj = nullptr;
+    double *const final_state = nullptr;
+    double *const moments = nullptr;
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
 }
 
 // ------------------------------------------------------------------------------------
@@ -1176,205 +1068,27 @@ rollout_quad3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__re
                      double *__restrict__ traj, double *__restrict__ final_state,
                      double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
 {
-    side_flag(side);
-    if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
-        side_cov_tile<8, kRollBlock>(side);
-        return;
-    }
-    // This wave's speed IS the iteration time: first in line at the instruction arbiter when a
-    // covariance workgroup of the same launch (or, multi-GPU, a collective's wave) lands on its
-    // SIMD.  (Reserving the SIMD outright -- allocating all 512 registers by touching v255 / a255
-    // -- measured neutral on one GPU and would serialise the covariance workgroups behind the
-    // rollouts once a batch fills the chip, so it is not done.)
-    __builtin_amdgcn_s_setprio(3);
-    constexpr int D = 8, M = 2;
-    const int lane = threadIdx.x;
-    const int q = lane & 3;
-    const int seg = (q == 3) ? 0 : q;              // lane 3 mirrors lane 0
-    const int64_t r_raw = (int64_t)blockIdx.x * kMomGroup + (lane >> 2);
-    const bool valid = r_raw < n_roll;
-    const int64_t r = valid ? r_raw : n_roll - 1;  // surplus quads recompute the last rollout
-    const sw::Quad3Lane L = sw::quad3_lane(seg);
-    const int cth = 2 + 2 * seg, cthd = 3 + 2 * seg;
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_quad3.inc"
+#undef SW_GATE_BODY
+}
 
-    // ---- this lane's policy row: V_i = c12 (W_{i-1} - W_i), W = (P +- nu delta) diag(inv_std)
-    // (ars_agent.py:141-142, environment.py:32-34), u_{-1} = u_2 = 0 (free ends); columns in
-    // this lane's rotated order [Gdx, Gdy, th_i, thd_i, th_i1, thd_i1, th_i2, thd_i2]
-    const int seg1 = (seg + 1) % 3, seg2 = (seg + 2) % 3;
-    const int cols[D] = {0, 1, cth, cthd, 2 + 2 * seg1, 3 + 2 * seg1, 2 + 2 * seg2, 3 + 2 * seg2};
-    double V[D], nbias;   // nbias = -V . mean: tq = V . (obs - mean) without per-step subtractions
-    load_policy_row<D, M, ARS>(ARS ? policies : policies + r * (M * D),
-                               ARS ? deltas + (dir_begin + (r >> 1)) * (M * D) : nullptr,
-                               (r & 1) ? -1.0 : 1.0, nu, mean, inv_std, C.c12, seg, cols, V, nbias);
-
-    // ---- start state ----
-    double gdx = 0.0, gdy = 0.0, th = kHalfPi, thd = 0.0;
-    if (state0) {
-        gdx = state0[r];
-        gdy = state0[n_roll + r];
-        th = state0[(int64_t)cth * n_roll + r];
-        thd = state0[(int64_t)cthd * n_roll + r];
-    }
-    // Trajectory stores go through a buffer resource (SGPR base + per-step SGPR offset +
-    // per-lane VGPR offset): one store instruction per value and one scalar add per step,
-    // no per-store 64-bit address arithmetic.  The host picks this kernel only when the
-    // whole trajectory buffer is < 4 GiB (32-bit offsets; out-of-range stores are dropped
-    // by the hardware range check, never written elsewhere).
-    const uint32_t off_th = (uint32_t)(((int64_t)cth * n_roll + r) * 8);
-    const uint32_t off_thd = (uint32_t)(((int64_t)cthd * n_roll + r) * 8);
-    // Gdot is replicated on every lane (each lane integrates its own copy, equal up to rounding):
-    // lanes of segment 0 record (store and sum) x, the others y.  ONE store of a per-lane selected
-    // value: a store costs ~16 issue cycles (measured), the select 2 x 4.4.  The rollout's
-    // Gdot_y is lane 1's copy: lane 2's store is dropped by the buffer range check.
-    const uint32_t kDrop = 0xfffffff0u;
-    const uint32_t off_g = (q == 2) ? kDrop : (uint32_t)(((int64_t)(seg == 0 ? 0 : 1) * n_roll + r) * 8);
-    const double selx = (seg == 0) ? 1.0 : 0.0, sely = 1.0 - selx;
-    const uint32_t slab = (uint32_t)(D * n_roll * 8);
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(
-        traj, 0, TRAJ ? (int)(uint32_t)((int64_t)H * slab) : 0, 0x00020000);
-    uint32_t soff = 0;
-    auto store_cell = [&](double v, uint32_t voff) {
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        union { double d; v2i i; } u;
-        u.d = v;
-        __builtin_amdgcn_raw_buffer_store_b64(u.i, trs, (int)voff, (int)soff, SW_TRAJ_STORE_AUX);
-    };
-
-    // The angle is carried in reduced form theta = r + K pi/2 (swimmer_device.h, Angle): no
-    // per-step range reduction or quadrant logic in sin / cos.
-    sw::Angle A = sw::angle_make(th);
-    double thmax = 0.0, det = 1.0;
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(thmax) : "v"(thmax), "v"(th));
-    double m1th = 0.0, m2th = 0.0, m1thd = 0.0, m2thd = 0.0;
-    double m1g = 0.0, m2g = 0.0;   // sums of this lane's Gdot component and its square
-    // neighbours' angular velocities for the next step: exchanged at the END of a step (behind
-    // the stores and moment updates), so the DPP reads never wait on the Euler update that just
-    // wrote them.  The neighbours' ANGLES are never exchanged: the policy is linear in them and
-    // theta_j(t+1) = theta_j(t) + h thetadot_j(t), so the angle part of this lane's torque balance,
-    //     Th(t) = -V . mean + sum_j V[theta_j] theta_j(t),
-    // is carried along as Th(t+1) = Th(t) + sum_j (h V[theta_j]) thetadot_j(t) -- three FMAs on
-    // velocities that are exchanged anyway, instead of three FMAs on angles plus four DPP moves.
-    // (It also spares the per-step cancellation of V . theta against V . mean, ~1e4 against ~1
-    // once the whitening is on.)
-    double w1 = sw::dpp_f64<sw::kDppNext1>(thd), w2 = sw::dpp_f64<sw::kDppNext2>(thd);
-    double Th = __builtin_fma(V[2], th, nbias);
-    Th = __builtin_fma(V[4], sw::dpp_f64<sw::kDppNext1>(th), Th);
-    Th = __builtin_fma(V[6], sw::dpp_f64<sw::kDppNext2>(th), Th);
-    const double hV2 = C.h * V[2], hV4 = C.h * V[4], hV6 = C.h * V[6];
-    const sw::TrigK K = sw::trig_consts();
-    double magic = 6755399441055744.0;   // 1.5 * 2^52, pinned in a VGPR pair for angle_keep_reduced
-    asm volatile("" : "+v"(magic));
-    sw::Quad3Geo G = sw::quad3_geometry(A, K), Gn;
-    // one step: consumes the geometry Gc of theta_t, produces Gx for theta_{t+1}
-    auto one_step = [&](const sw::Quad3Geo &Gc, sw::Quad3Geo &Gx) {
-        // this segment's torque balance c12 (u_{i-1} - u_i) = V_i . (obs - mean): the carried
-        // angle part + the velocity part (the neighbours' angular velocities arrive by DPP and are
-        // reused by the physics step).  One accumulator: the kernel is issue-bound, not chain-bound.
-        // theta_{t+1} needs thetadot_t only: advance the angle first and start its range test; the
-        // policy's eight FMAs sit between the vector compare and the scalar branch that waits for it.
-        // Its sin / cos and the neighbour exchange run beside this step's solve (software pipelining
-        // across steps, swimmer_quad3.h)
-        A.r = __builtin_fma(C.h, thd, A.r);
-        const unsigned long long outside = sw::angle_range_test(A.r);
-        double tq = __builtin_fma(V[0], gdx, Th);
-        tq = __builtin_fma(V[1], gdy, tq);
-        tq = __builtin_fma(V[3], thd, tq);
-        tq = __builtin_fma(V[5], w1, tq);
-        tq = __builtin_fma(V[7], w2, tq);
-        Th = __builtin_fma(hV2, thd, Th);
-        Th = __builtin_fma(hV4, w1, Th);
-        Th = __builtin_fma(hV6, w2, Th);
-        sw::angle_keep_reduced(A, thmax, magic, outside);   // untaken branch; rare re-normalisation
-        const double th_next = sw::angle_theta(A);
-        Gx = sw::quad3_geometry(A, K);
-        det = sw::quad3_dynamics(C, L, Gc, gdx, gdy, thd, w1, w2, tq);
-        th = th_next;
-        // the return comes out of the per-component sums in the epilogue (linearity), no
-        // per-step reward arithmetic
-        const double gsel = __builtin_fma(selx, gdx, sely * gdy);
-        m1g += gsel;
-        if (TRAJ) {
-            store_cell(th, off_th);
-            store_cell(thd, off_thd);
-            store_cell(gsel, off_g);
-            soff += slab;
-        }
-        if (MOM) {
-            const double a = th - kHalfPi;
-            m1th += a;
-            m2th = __builtin_fma(a, a, m2th);
-            m1thd += thd;
-            m2thd = __builtin_fma(thd, thd, m2thd);
-            m2g = __builtin_fma(gsel, gsel, m2g);
-        }
-        w1 = sw::dpp_f64<sw::kDppNext1>(thd);
-        w2 = sw::dpp_f64<sw::kDppNext2>(thd);
-    };
-    // four steps per trip, the geometry ping-pongs between G and Gn (no register copies)
-    int32_t t = 0;
-#if SW_QUAD_UNROLL == 4
-    SW_PIN_LOOP(SW_QUAD_LOOP_PAD);
-    for (; t + 4 <= H; t += 4) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-    }
-#endif
-    for (; t + 2 <= H; t += 2) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-    }
-    if (t < H) one_step(G, Gn);
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(thmax) : "v"(thmax), "v"(th));
-    // the joint-acceleration system is the chain's (scaled) mass matrix: positive definite for
-    // every finite configuration, so its determinant can only fail to be positive once the state
-    // is no longer finite -- the last step's says so
-    const double detmin = det;
-
-    // ---- per-rollout outputs (quad lanes 0..2 hold the state; lane 0 the return) ----
-    int code = ((detmin > 0.0) ? 0 : SW_STATUS_SINGULAR) |
-               ((isfinite(th) && isfinite(thd) && isfinite(gdx) && isfinite(gdy)) ? 0 : SW_STATUS_NONFINITE) |
-               ((thmax < sw::kAngleLimit) ? 0 : SW_STATUS_RANGE);
-    code |= __builtin_amdgcn_mov_dpp(code, sw::kDppNext1, 0xf, 0xf, true) |
-            __builtin_amdgcn_mov_dpp(code, sw::kDppNext2, 0xf, 0xf, true);
-    // sum of the rewards Gdot_t . direction (remy_swimmer_env.py:238-243), by linearity:
-    // lane 0 holds sum Gdot_x, lane 1 sum Gdot_y
-    const double sgy = sw::dpp_f64<sw::kDppNext1>(m1g);
-    if (valid && q == 0) {
-        const double total = __builtin_fma(C.dirx, m1g, C.diry * sgy);
-        returns[r] = (code & SW_STATUS_RANGE) ? __builtin_nan("") : total;
-        if (status) status[r] = code;
-    }
-    if (final_state && valid && q < 3) {
-        final_state[(int64_t)cth * n_roll + r] = th;
-        final_state[(int64_t)cthd * n_roll + r] = thd;
-        if (q < 2) final_state[(int64_t)q * n_roll + r] = (q == 0) ? gdx : gdy;
-    }
-    if (MOM) {
-        if (!valid) m1th = m2th = m1thd = m2thd = m1g = m2g = 0.0;
-        // sum over the 16 rollouts of the wave, per segment lane: xor-butterfly over lane>>2
-#pragma unroll
-        for (int off = 4; off < kWave; off <<= 1) {
-            m1th += __shfl_xor(m1th, off, kWave);
-            m2th += __shfl_xor(m2th, off, kWave);
-            m1thd += __shfl_xor(m1thd, off, kWave);
-            m2thd += __shfl_xor(m2thd, off, kWave);
-            m1g += __shfl_xor(m1g, off, kWave);
-            m2g += __shfl_xor(m2g, off, kWave);
-        }
-        if (lane < 3) {
-            double *row = moments + (int64_t)blockIdx.x * (2 * D);
-            row[cth] = m1th;
-            row[cthd] = m1thd;
-            row[D + cth] = m2th;
-            row[D + cthd] = m2thd;
-            if (lane < 2) {
-                row[lane] = m1g;
-                row[D + lane] = m2g;
-            }
-        }
-    }
+// The ARS simulator gate (sw_ars_gate_f64) in the quad form (body: swimmer_rollout_quad3.inc).
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_quad3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                      const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                      const double *__restrict__ mean, const double *__restrict__ inv_std, double gate_thr,
+                      int32_t *__restrict__ admit, double *__restrict__ returns, int32_t *__restrict__ status,
+                      SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+    const double *const state0 = nullptr;
+    double *const traj = nullptr;
+    double *const final_state = nullptr;
+    double *const moments = nullptr;
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_quad3.inc"
+#undef SW_GATE_BODY
 }
 
 // ------------------------------------------------------------------------------------
@@ -1389,200 +1103,27 @@ rollout_oct3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__res
                     double *__restrict__ traj, double *__restrict__ final_state,
                     double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
 {
-    side_flag(side);
-    if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
-        side_cov_tile<8, kOctBlock>(side);
-        return;
-    }
-    __builtin_amdgcn_s_setprio(3);   // as in the quad kernel
-    constexpr int D = 8, M = 2;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int q = lane & 3;
-    const int seg = (q == 3) ? 0 : q;              // lane 3 of a quad mirrors lane 0
-    const bool cosine = (lane & 8) != 0;           // quad B of the rollout: cosine / Gdot_y roles
-    const int64_t r_raw = (int64_t)blockIdx.x * kMomGroup + wave * 8 + (lane >> 4) * 2 + ((lane >> 2) & 1);
-    const bool valid = r_raw < n_roll;
-    const int64_t r = valid ? r_raw : n_roll - 1;  // surplus rollouts recompute the last one
-    const sw::OctLane O = sw::oct3_lane(C, seg, cosine);
-    const int cth = 2 + 2 * seg, cthd = 3 + 2 * seg;
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_oct3.inc"
+#undef SW_GATE_BODY
+}
 
-    // this lane's policy row in its rotated order [Gdx, Gdy, th_i, thd_i, th_i1, thd_i1, th_i2, thd_i2]
-    const int seg1 = (seg + 1) % 3, seg2 = (seg + 2) % 3;
-    const int cols[D] = {0, 1, cth, cthd, 2 + 2 * seg1, 3 + 2 * seg1, 2 + 2 * seg2, 3 + 2 * seg2};
-    double V[D], nbias;
-    load_policy_row<D, M, ARS>(ARS ? policies : policies + r * (M * D),
-                               ARS ? deltas + (dir_begin + (r >> 1)) * (M * D) : nullptr,
-                               (r & 1) ? -1.0 : 1.0, nu, mean, inv_std, C.c12, seg, cols, V, nbias);
-    // Gdot in the roles: Pu = the component this quad integrates, Pv = its partner's
-    const double VPu = cosine ? V[1] : V[0], VPv = cosine ? V[0] : V[1];
-
-    double gdx = 0.0, gdy = 0.0, th = kHalfPi, thd = 0.0;
-    if (state0) {
-        gdx = state0[r];
-        gdy = state0[n_roll + r];
-        th = state0[(int64_t)cth * n_roll + r];
-        thd = state0[(int64_t)cthd * n_roll + r];
-    }
-    double Pu = cosine ? gdy : gdx, Pv = cosine ? gdx : gdy;
-
-    // trajectory cells through a buffer resource (as in the quad kernel); quad A records theta,
-    // thetadot and Gdot_x, quad B Gdot_y; every other lane's store is dropped by the range check
-    const uint32_t kDrop = 0xfffffff0u;
-    const bool rec = !cosine && q < 3;
-    const uint32_t off_th = rec ? (uint32_t)(((int64_t)cth * n_roll + r) * 8) : kDrop;
-    const uint32_t off_thd = rec ? (uint32_t)(((int64_t)cthd * n_roll + r) * 8) : kDrop;
-    const uint32_t off_g = (q == 0) ? (uint32_t)(((int64_t)(cosine ? 1 : 0) * n_roll + r) * 8) : kDrop;
-    const uint32_t slab = (uint32_t)(D * n_roll * 8);
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(
-        traj, 0, TRAJ ? (int)(uint32_t)((int64_t)H * slab) : 0, 0x00020000);
-    uint32_t soff = 0;
-    auto store_cell = [&](double v, uint32_t voff) {
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        union { double d; v2i i; } u;
-        u.d = v;
-        __builtin_amdgcn_raw_buffer_store_b64(u.i, trs, (int)voff, (int)soff, SW_TRAJ_STORE_AUX);
-    };
-
-    // the angle in reduced form + the polynomial this lane currently evaluates (swimmer_oct3.h)
-    const int designation = cosine ? 1 : 0;
-    double thmax = 0.0, det = 1.0;
-    sw::OctTrig A;
-    A.r = th;
-    A.kd = 0.0;
-    sw::oct3_renorm(A, designation, thmax);
-    double m1th = 0.0, m2th = 0.0, m1thd = 0.0, m2thd = 0.0, m1g = 0.0, m2g = 0.0;
-    double w1 = sw::dpp_f64<sw::kDppNext1>(thd), w2 = sw::dpp_f64<sw::kDppNext2>(thd);
-    double Th = __builtin_fma(V[2], th, nbias);
-    Th = __builtin_fma(V[4], sw::dpp_f64<sw::kDppNext1>(th), Th);
-    Th = __builtin_fma(V[6], sw::dpp_f64<sw::kDppNext2>(th), Th);
-    const double hV2 = C.h * V[2], hV4 = C.h * V[4], hV6 = C.h * V[6];
-    sw::OctGeo G = sw::oct3_geometry(A), Gn;
-    double magic = 6755399441055744.0;   // 1.5 * 2^52, pinned in a VGPR pair for oct3_keep_reduced
-    asm volatile("" : "+v"(magic));
-    auto one_step = [&](const sw::OctGeo &Gc, sw::OctGeo &Gx) {
-        // theta_{t+1} needs thetadot_t only: advance the angle first and start its range test, the
-        // policy's eight FMAs sit between the vector compare and the scalar branch that waits for it
-        A.r = __builtin_fma(C.h, thd, A.r);
-        const unsigned long long outside = sw::oct3_range_test(A.r);
-        double tq = __builtin_fma(VPu, Pu, Th);
-        tq = __builtin_fma(VPv, Pv, tq);
-        tq = __builtin_fma(V[3], thd, tq);
-        tq = __builtin_fma(V[5], w1, tq);
-        tq = __builtin_fma(V[7], w2, tq);
-        Th = __builtin_fma(hV2, thd, Th);
-        Th = __builtin_fma(hV4, w1, Th);
-        Th = __builtin_fma(hV6, w2, Th);
-        sw::oct3_keep_reduced(A, thmax, magic, designation, outside);   // untaken branch; rare re-normalisation
-        const double th_next = __builtin_fma(A.kd, sw::kPio2Hi, A.r);
-        Gx = sw::oct3_geometry(A);
-        det = sw::oct3_dynamics(C, O, Gc, Pu, Pv, thd, w1, w2, tq);
-        th = th_next;
-        m1g += Pu;
-        if (TRAJ) {
-            store_cell(th, off_th);
-            store_cell(thd, off_thd);
-            store_cell(Pu, off_g);
-            soff += slab;
-        }
-        if (MOM) {
-            const double a = th - kHalfPi;
-            m1th += a;
-            m2th = __builtin_fma(a, a, m2th);
-            m1thd += thd;
-            m2thd = __builtin_fma(thd, thd, m2thd);
-            m2g = __builtin_fma(Pu, Pu, m2g);
-        }
-        w1 = sw::dpp_f64<sw::kDppNext1>(thd);
-        w2 = sw::dpp_f64<sw::kDppNext2>(thd);
-        Pv = sw::dpp_row_f64<sw::kDppRowRor8>(Pu);
-    };
-    // the geometry ping-pongs between G and Gn (no register copies): an even number of steps per trip
-    int32_t t = 0;
-    SW_PIN_LOOP(oct_loop_pad(TRAJ, MOM));
-#if SW_OCT_UNROLL == 8
-    // eight steps per trip: the loop's back edge costs a lone wave ~8-13 ns (2 / 4 / 8 steps per trip:
-    // 0.2292 / 0.2272 / 0.2250 ms per launch, each at its best loop offset; profiles/r03_t, r03_w)
-    for (; t + 8 <= H; t += 8) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-    }
-#endif
-    for (; t + 4 <= H; t += 4) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-    }
-    for (; t + 2 <= H; t += 2) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-    }
-    if (t < H) one_step(G, Gn);
-    thmax = fmax(thmax, fabs(th));
-
-    // ---- per-rollout outputs: quad A lanes 0..2 hold (theta, thetadot), A lane 0 Gdot_x, B lane 0 Gdot_y
-    int code = ((det > 0.0) ? 0 : SW_STATUS_SINGULAR) |
-               ((isfinite(th) && isfinite(thd) && isfinite(Pu) && isfinite(Pv)) ? 0 : SW_STATUS_NONFINITE) |
-               ((thmax < sw::kAngleLimit) ? 0 : SW_STATUS_RANGE);
-    code |= __builtin_amdgcn_mov_dpp(code, sw::kDppNext1, 0xf, 0xf, true) |
-            __builtin_amdgcn_mov_dpp(code, sw::kDppNext2, 0xf, 0xf, true);
-    code |= __builtin_amdgcn_mov_dpp(code, sw::kDppRowRor8, 0xf, 0xf, true);
-    const double sg_other = sw::dpp_row_f64<sw::kDppRowRor8>(m1g);   // on A: sum Gdot_y
-    if (valid && !cosine && q == 0) {
-        const double total = __builtin_fma(C.dirx, m1g, C.diry * sg_other);
-        returns[r] = (code & SW_STATUS_RANGE) ? __builtin_nan("") : total;
-        if (status) status[r] = code;
-    }
-    if (final_state && valid) {
-        if (rec) {
-            final_state[(int64_t)cth * n_roll + r] = th;
-            final_state[(int64_t)cthd * n_roll + r] = thd;
-        }
-        if (q == 0) final_state[(int64_t)(cosine ? 1 : 0) * n_roll + r] = Pu;
-    }
-    if (MOM) {
-        __shared__ double shm[kOctBlock / kWave][16][6];
-        if (!valid) m1th = m2th = m1thd = m2thd = m1g = m2g = 0.0;
-        // sum over the 8 rollouts of the wave, per (quad half, segment) lane: lane bits 2, 4, 5
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int off = (k == 0) ? 4 : (k == 1 ? 16 : 32);
-            m1th += __shfl_xor(m1th, off, kWave);
-            m2th += __shfl_xor(m2th, off, kWave);
-            m1thd += __shfl_xor(m1thd, off, kWave);
-            m2thd += __shfl_xor(m2thd, off, kWave);
-            m1g += __shfl_xor(m1g, off, kWave);
-            m2g += __shfl_xor(m2g, off, kWave);
-        }
-        if (lane < 16) {
-            shm[wave][lane][0] = m1th;
-            shm[wave][lane][1] = m2th;
-            shm[wave][lane][2] = m1thd;
-            shm[wave][lane][3] = m2thd;
-            shm[wave][lane][4] = m1g;
-            shm[wave][lane][5] = m2g;
-        }
-        __syncthreads();
-        // row lanes 0..2: segments (quad A); row lane 0: Gdot_x sums; row lane 8: Gdot_y sums (quad B)
-        if (tid < 3) {
-            double *row = moments + (int64_t)blockIdx.x * (2 * D);
-            row[2 + 2 * tid] = shm[0][tid][0] + shm[1][tid][0];
-            row[D + 2 + 2 * tid] = shm[0][tid][1] + shm[1][tid][1];
-            row[3 + 2 * tid] = shm[0][tid][2] + shm[1][tid][2];
-            row[D + 3 + 2 * tid] = shm[0][tid][3] + shm[1][tid][3];
-            if (tid < 2) {
-                const int src = tid * 8;
-                row[tid] = shm[0][src][4] + shm[1][src][4];
-                row[D + tid] = shm[0][src][5] + shm[1][src][5];
-            }
-        }
-    }
+// The ARS simulator gate (sw_ars_gate_f64) in the mirror-quad form (body: swimmer_rollout_oct3.inc).
+__global__ void __launch_bounds__(kOctBlock)
+ars_gate_oct3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                     const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                     const double *__restrict__ mean, const double *__restrict__ inv_std, double gate_thr,
+                     int32_t *__restrict__ admit, double *__restrict__ returns, int32_t *__restrict__ status,
+                     SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+    const double *const state0 = nullptr;
+    double *const traj = nullptr;
+    double *const final_state = nullptr;
+    double *const moments = nullptr;
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_oct3.inc"
+#undef SW_GATE_BODY
 }
 
 // ------------------------------------------------------------------------------------
@@ -1769,201 +1310,28 @@ rollout_row_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__rest
                    double *__restrict__ traj, double *__restrict__ final_state,
                    double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
 {
-    side_flag(side);
-    if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
-        side_cov_tile<2 * N + 2, kRowBlock>(side);
-        return;
-    }
-    __builtin_amdgcn_s_setprio(3);   // as in the quad kernel
-    constexpr int D = 2 * N + 2, M = N - 1;
-    const int tid = threadIdx.x;
-    const int q = tid & 15;                        // lane inside the row
-    const bool owner = q < N;                      // lanes 0..N-1 own the segments' cells
-    const bool cosine = q >= 8;                    // lane i + 8 mirrors lane i and evaluates the cosine
-    const int seg = ((q & 7) < N) ? (q & 7) : 0;   // lanes N..7 / N+8..15 mirror lane 0 / 8
-    const int64_t r_raw = (int64_t)blockIdx.x * kMomGroup + (tid >> 4);
-    const bool valid = r_raw < n_roll;
-    const int64_t r = valid ? r_raw : n_roll - 1;  // surplus rows recompute the last rollout
-    const sw::RowLane<N> L = sw::row_lane<N>(C, seg);
-    const int cth = 2 + 2 * seg, cthd = 3 + 2 * seg;
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_row.inc"
+#undef SW_GATE_BODY
+}
 
-    // ---- this lane's policy row: V_i = c12 (W_{i-1} - W_i), W = (P +- nu delta) diag(inv_std)
-    // (ars_agent.py:141-142, environment.py:32-34); u_{-1} = u_{n-1} = 0 (free ends)
-    double V[D], nbias;   // nbias = -V . mean: tq = V . (obs - mean) without per-step subtractions
-    {
-        int cols[D];
-#pragma unroll
-        for (int j = 0; j < D; ++j) cols[j] = j;   // canonical order
-        load_policy_row<D, M, ARS>(ARS ? policies : policies + r * (M * D),
-                                   ARS ? deltas + (dir_begin + (r >> 1)) * (M * D) : nullptr,
-                                   (r & 1) ? -1.0 : 1.0, nu, mean, inv_std, C.c12, seg, cols, V, nbias);
-    }
-
-    // ---- start state ----
-    double gdx = 0.0, gdy = 0.0, th = kHalfPi, thd = 0.0;
-    if (state0) {
-        gdx = state0[r];
-        gdy = state0[n_roll + r];
-        th = state0[(int64_t)cth * n_roll + r];
-        thd = state0[(int64_t)cthd * n_roll + r];
-    }
-    // trajectory cells through a buffer resource; lanes that own no cell get an offset
-    // beyond the buffer, which the hardware range check drops
-    const uint32_t slab = (uint32_t)(D * n_roll * 8);
-    const uint32_t kDrop = 0xfffffff0u;
-    const uint32_t off_th = (owner && valid) ? (uint32_t)(((int64_t)cth * n_roll + r) * 8) : kDrop;
-    const uint32_t off_thd = (owner && valid) ? (uint32_t)(((int64_t)cthd * n_roll + r) * 8) : kDrop;
-    // Gdot is replicated (bit-identical on all lanes): lane 0 stores x, lane 1 stores y, with two
-    // store instructions.  (The quad kernel's per-lane select + single store has the same
-    // instruction count here but measured 5 % slower: the select lands on the serial chain.)
-    const uint32_t off_gx = (q == 0 && valid) ? (uint32_t)(r * 8) : kDrop;
-    const uint32_t off_gy = (q == 1 && valid) ? (uint32_t)((n_roll + r) * 8) : kDrop;
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(
-        traj, 0, TRAJ ? (int)(uint32_t)((int64_t)H * slab) : 0, 0x00020000);
-    uint32_t soff = 0;
-    auto store_cell = [&](double v, uint32_t voff) {
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        union { double d; v2i i; } u;
-        u.d = v;
-        __builtin_amdgcn_raw_buffer_store_b64(u.i, trs, (int)voff, (int)soff, SW_TRAJ_STORE_AUX);
-    };
-
-    double thmax = 0.0, rq_last = 1.0;
-    double m1th = 0.0, m2th = 0.0, m1thd = 0.0, m2thd = 0.0;
-    double sgx = 0.0, sgy = 0.0, qgx = 0.0, qgy = 0.0;   // sums of Gdot and Gdot^2 over the steps
-    // theta = r + K pi/2 and the polynomial this lane evaluates of r (swimmer_oct3.h, OctTrig)
-    const int designation = cosine ? 1 : 0;
-    sw::OctTrig A;
-    A.r = th;
-    A.kd = 0.0;
-    sw::oct3_renorm(A, designation, thmax);
-    // one step: policy + physics (swimmer_row.h; the other segments' angles and angular velocities are
-    // read straight out of their lanes by fused broadcast-FMAs), then the step's records
-    auto one_step = [&](auto slow) {
-        const double rq = sw::row_step<N, decltype(slow)::value>(C, L, V, nbias, cosine, designation, gdx, gdy,
-                                                                 A, th, thd, thmax);
-        rq_last = rq;   // the system is the chain's mass matrix: a pivot can only fail to be positive once the
-                        // state is no longer finite, and then the last step's says so
-        // the return comes out of the per-component sums in the epilogue (linearity)
-        sgx += gdx;
-        sgy += gdy;
-        if (TRAJ) {
-            store_cell(th, off_th);
-            store_cell(thd, off_thd);
-            store_cell(gdx, off_gx);
-            store_cell(gdy, off_gy);
-            soff += slab;
-        }
-        if (MOM) {
-            const double a = th - kHalfPi;
-            m1th += a;
-            m2th = __builtin_fma(a, a, m2th);
-            m1thd += thd;
-            m2thd = __builtin_fma(thd, thd, m2thd);
-            qgx = __builtin_fma(gdx, gdx, qgx);
-            qgy = __builtin_fma(gdy, gdy, qgy);
-        }
-    };
-    // Range check once per trip of four steps (the mirror-quad kernel's per-step asm check would cost
-    // registers this kernel does not have at n >= 6): a trip whose angles move at most kTripSlack runs
-    // unchecked after one re-normalisation at its start if needed -- r ends at most that far past pi/4,
-    // where the polynomials are still accurate to 2.5e-16 (swimmer_oct3.h); a faster trip runs in the
-    // second loop, which checks inside every step (exact for any angular velocity).  What thetadot GAINS inside
-    // an unchecked trip is not in that bound: an angle travels up to 6 h^2 |thetadotdot| further (0.06 rad at
-    // 10 000 rad/s^2) before the next trip start sees the speed.  The polynomials degrade smoothly out there --
-    // 2.0e-16 at pi/4 + 0.04, 1.7e-15 at + 0.10, 9e-14 at + 0.25 (tests/test_trig_range.py) -- and rollouts with
-    // first-step accelerations of 3 000 ... 20 000 rad/s^2 stay within 1e-6 (relative) of the oracle
-    // (tests/test_hip_parity.py::test_violent_accelerations_inside_an_unchecked_trip).  One step per loop
-    // body either way: unrolled, n >= 6 would leave the 256 architectural registers.
-    auto too_fast = [&]() -> bool {
-        return __any((4.0 * C.h) * fabs(thd) > sw::kTripSlack);
-    };
-    int32_t t = 0;
-    SW_PIN_LOOP(row_loop_pad(N, TRAJ, MOM));
-    while (t < H) {   // two loops, not one loop with two bodies: merged, the compiler reconciles the bodies'
-                      // register assignments with copies on the common path (profiles/r03_g_ab_range_check_variants.log)
-        while (t < H) {                              // unchecked trips of (up to) four steps
-            if (__builtin_expect(too_fast(), 0)) break;
-            const double reach = __builtin_fma(4.0 * C.h, fabs(thd), fabs(A.r));
-            if (__builtin_expect(__any(reach > sw::kPio4), 0)) sw::oct3_renorm(A, designation, thmax);
-            const int32_t t_end = min(H, t + 4);
-#pragma unroll 1
-            for (; t < t_end; ++t) one_step(std::false_type{});
-        }
-#pragma unroll 1
-        for (; t < H && too_fast(); ++t) one_step(std::true_type{});   // checks inside every step
-    }
-
-    thmax = fmax(thmax, fabs(th));
-    // ---- per-rollout outputs ----
-    {
-        double bad[N], big[N], piv[N];
-        const bool fin = isfinite(th) && isfinite(thd) && isfinite(gdx) && isfinite(gdy);
-        sw::RowGather<N>::run(fin ? 0.0 : 1.0, bad);
-        sw::RowGather<N>::run(thmax, big);
-        sw::RowGather<N>::run(rq_last, piv);      // every segment lane's last 1 / pivot
-        double nbad = 0.0, tmax = 0.0, pmin = 1.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            nbad += bad[k];
-            tmax = fmax(tmax, big[k]);
-            pmin = fmin(pmin, piv[k]);
-        }
-        const int code = ((pmin > 0.0) ? 0 : SW_STATUS_SINGULAR) |
-                         ((nbad == 0.0) ? 0 : SW_STATUS_NONFINITE) |
-                         ((tmax < sw::kAngleLimit) ? 0 : SW_STATUS_RANGE);
-        if (valid && q == 0) {
-            // sum of the rewards Gdot_t . direction (remy_swimmer_env.py:238-243), by linearity
-            const double total = __builtin_fma(C.dirx, sgx, C.diry * sgy);
-            returns[r] = (code & SW_STATUS_RANGE) ? __builtin_nan("") : total;
-            if (status) status[r] = code;
-        }
-    }
-    if (final_state && valid && owner) {
-        final_state[(int64_t)cth * n_roll + r] = th;
-        final_state[(int64_t)cthd * n_roll + r] = thd;
-        if (q < 2) final_state[(int64_t)q * n_roll + r] = (q == 0) ? gdx : gdy;
-    }
-    if (MOM) {
-        __shared__ double shm[kRowBlock / kWave][16][6];
-        double m1g = (q == 0) ? sgx : sgy, m2g = (q == 0) ? qgx : qgy;   // lane 0: x, lane 1: y
-        if (!valid || !owner) m1th = m2th = m1thd = m2thd = m1g = m2g = 0.0;
-        // sum over the 4 rows of the wave (lane bits 4, 5), then over the 4 waves through LDS
-#pragma unroll
-        for (int off = 16; off < kWave; off <<= 1) {
-            m1th += __shfl_xor(m1th, off, kWave);
-            m2th += __shfl_xor(m2th, off, kWave);
-            m1thd += __shfl_xor(m1thd, off, kWave);
-            m2thd += __shfl_xor(m2thd, off, kWave);
-            m1g += __shfl_xor(m1g, off, kWave);
-            m2g += __shfl_xor(m2g, off, kWave);
-        }
-        const int wv = tid / kWave, ln = tid % kWave;
-        if (ln < 16) {
-            shm[wv][ln][0] = m1th;
-            shm[wv][ln][1] = m2th;
-            shm[wv][ln][2] = m1thd;
-            shm[wv][ln][3] = m2thd;
-            shm[wv][ln][4] = m1g;
-            shm[wv][ln][5] = m2g;
-        }
-        __syncthreads();
-        if (tid < N) {
-            double acc[6];
-#pragma unroll
-            for (int v = 0; v < 6; ++v)
-                acc[v] = (shm[0][tid][v] + shm[1][tid][v]) + (shm[2][tid][v] + shm[3][tid][v]);
-            double *row = moments + (int64_t)blockIdx.x * (2 * D);
-            row[2 + 2 * tid] = acc[0];
-            row[D + 2 + 2 * tid] = acc[1];
-            row[3 + 2 * tid] = acc[2];
-            row[D + 3 + 2 * tid] = acc[3];
-            if (tid < 2) {
-                row[tid] = acc[4];
-                row[D + tid] = acc[5];
-            }
-        }
-    }
+// The ARS simulator gate (sw_ars_gate_f64) in the row form, n = 4..8 (body: swimmer_rollout_row.inc).
+template <int N>
+__global__ void __launch_bounds__(kRowBlock, (N <= 6 ? 2 : 1))
+ars_gate_row_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                    const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                    const double *__restrict__ mean, const double *__restrict__ inv_std, double gate_thr,
+                    int32_t *__restrict__ admit, double *__restrict__ returns, int32_t *__restrict__ status,
+                    SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+    const double *const state0 = nullptr;
+    double *const traj = nullptr;
+    double *const final_state = nullptr;
+    double *const moments = nullptr;
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_row.inc"
+#undef SW_GATE_BODY
 }
 
 // ------------------------------------------------------------------------------------
@@ -2905,6 +2273,60 @@ int sw_ars_rollouts_f64(const sw_params *p, int64_t dir_begin, int64_t n_dir, in
     (void)hipGetLastError();   // public entry point: drop a stale error once (see check_params)
     return launch_ars_rollouts(p, dir_begin, n_dir, H, policy, deltas, nu, mean, inv_std, returns,
                                traj, moments, status, stream, nullptr, nullptr);
+}
+
+// The ARS simulator gate (ars_agent.py:144-157): the 2 n_dir simulator rollouts of launch_ars_rollouts in
+// the form it would pick without trajectories, returns only, the decision fused into the epilogue.
+int sw_ars_gate_f64(const sw_params *sim, int64_t dir_begin, int64_t n_dir, int32_t H, const double *policy,
+                    const double *deltas, double nu, const double *mean, const double *inv_std,
+                    double sim_thresh, int32_t *admit, double *returns, int32_t *status, void *stream)
+{
+    (void)hipGetLastError();   // public entry point: drop a stale error once (see check_params)
+    int rc = validate_params(sim);
+    if (rc) return rc;
+    if (n_dir < 0 || H < 0 || dir_begin < 0) return SW_ERR_SIZE;
+    if (n_dir == 0) return SW_OK;
+    if (!policy || !deltas || !admit) return SW_ERR_NULL;
+    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
+    const sw::Consts C = make_consts(sim);
+    const int64_t n_roll = 2 * n_dir;
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned rows = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
+    if (use_oct3(sim, n_roll, H, false)) {
+        hipLaunchKernelGGL(ars_gate_oct3_kernel, dim3(rows), dim3(kOctBlock), 0, st, C, n_roll, H, policy, deltas,
+                           dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status, kNoSide);
+        return launch_status();
+    }
+    if (use_quad3(sim, n_roll, H, false)) {
+        hipLaunchKernelGGL(ars_gate_quad3_kernel, dim3(rows), dim3(kRollBlock), 0, st, C, n_roll, H, policy, deltas,
+                           dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status, kNoSide);
+        return launch_status();
+    }
+    if (use_row(sim, n_roll, H, false)) {
+        switch (sim->n) {
+#define SW_GATE_ROW(NN)                                                                                           \
+    case NN:                                                                                                      \
+        hipLaunchKernelGGL(ars_gate_row_kernel<NN>, dim3(rows), dim3(kRowBlock), 0, st, C, n_roll, H, policy,    \
+                           deltas, dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status, kNoSide);    \
+        break;
+        SW_GATE_ROW(4) SW_GATE_ROW(5) SW_GATE_ROW(6) SW_GATE_ROW(7) SW_GATE_ROW(8)
+#undef SW_GATE_ROW
+        default: return SW_ERR_SEGMENTS;
+        }
+        return launch_status();
+    }
+    const unsigned grid = (unsigned)((n_roll + kRollBlock - 1) / kRollBlock);
+    const sw::TwinConsts T = make_twin_consts(sim);
+    if (is_twin(sim)) {
+        SW_DISPATCH_N(sim->n, hipLaunchKernelGGL((ars_gate_kernel<NN, true>), dim3(grid), dim3(kRollBlock), 0, st, C,
+                                                 T, n_roll, H, policy, deltas, dir_begin, nu, mean, inv_std,
+                                                 sim_thresh, admit, returns, status));
+    } else {
+        SW_DISPATCH_N(sim->n, hipLaunchKernelGGL((ars_gate_kernel<NN, false>), dim3(grid), dim3(kRollBlock), 0, st, C,
+                                                 T, n_roll, H, policy, deltas, dir_begin, nu, mean, inv_std,
+                                                 sim_thresh, admit, returns, status));
+    }
+    return launch_status();
 }
 
 static int launch_update(const sw_params *p, int64_t n_dir, const GatherView &gv,

@@ -282,6 +282,40 @@ def ars_rollouts(p: SwParams, H: int, policy, deltas, nu: float, dir_begin: int,
     return returns
 
 
+def ars_gate(p_sim: SwParams, H: int, policy, deltas, nu: float, dir_begin: int, n_dir: int,
+             sim_thresh: float, mean=None, inv_std=None, returns=None, status=None, admit=None):
+    """The safe-ARS simulator gate (ars_agent.py:144-157): the 2*n_dir rollouts P +- nu*delta_i in the
+    simulator p_sim and, in the same launch, admit[j] = !(r_j+ <= sim_thresh) && !(r_j- <= sim_thresh).
+    Returns admit, an int32 device tensor [n_dir] (1 = take the real rollouts).  `returns` / `status`
+    ([2*n_dir], optional) receive the simulator returns / status codes as ars_rollouts writes them; `admit`
+    (optional) is an int32 [n_dir] tensor to write the flags into instead of a new one."""
+    require_gpu()
+    _want(policy, "policy", (p_sim.m, p_sim.d))
+    if deltas.dim() != 3 or deltas.shape[0] < dir_begin + n_dir:
+        raise _lib.SwimmerHipError("deltas: need [>= dir_begin + n_dir, m, d]")
+    _want(deltas, "deltas", (deltas.shape[0], p_sim.m, p_sim.d))
+    dev = policy.device
+    n_roll = 2 * n_dir
+    if (mean is None) != (inv_std is None):
+        raise _lib.SwimmerHipError("mean and inv_std must be given together")
+    if mean is not None:
+        _want(mean, "mean", (p_sim.d,))
+        _want(inv_std, "inv_std", (p_sim.d,))
+    if returns is not None:
+        _want(returns, "returns", (n_roll,))
+    if status is not None and (status.dtype != torch.int32 or tuple(status.shape) != (n_roll,)
+                               or status.device != dev):
+        raise _lib.SwimmerHipError(f"status: expected int32 tensor of shape ({n_roll},) on {dev}")
+    if admit is None:
+        admit = torch.empty(n_dir, dtype=torch.int32, device=dev)
+    elif admit.dtype != torch.int32 or tuple(admit.shape) != (n_dir,) or admit.device != dev:
+        raise _lib.SwimmerHipError(f"admit: expected int32 tensor of shape ({n_dir},) on {dev}")
+    check(load().sw_ars_gate_f64(ctypes.byref(p_sim), dir_begin, n_dir, H, ptr(policy), ptr(deltas),
+                                 float(nu), ptr(mean), ptr(inv_std), float(sim_thresh), ptr(admit),
+                                 ptr(returns), ptr(status), stream_ptr()), "sw_ars_gate_f64")
+    return admit
+
+
 def ars_update(p: SwParams, returns, deltas, policy, alpha: float, b: float, top_b: int = 0,
                moments=None, running=None, n_new_states: int = 0, mean=None, inv_std=None,
                sigma_out=None):

@@ -1,0 +1,202 @@
+"""ARSAgent(safe=True) and the gate kernel sw_ars_gate_f64 on the GPU: the reference's fixtures
+(tests/golden/safe_agent.npz), the gate against ars_rollouts in every kernel form, and the safe iteration against
+the unsafe one and against the CPU restatement (tests/safe_agent_oracle.py)."""
+import os
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import swimmer_amd as sw
+from swimmer_amd import kernels
+from swimmer_amd._lib import SwParams, kernel_flags
+from swimmer_amd.ars.parameters import Threshold
+from conftest import GOLDEN
+from safe_agent_oracle import SafeArsOracle
+from test_safe_ars_agent_cpu import DB, _close, _fixture, _params
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _agent_for_case(g, tag, tmp_path):
+    ep, ap, thresh, c = _params(g, tag)
+    w0 = str(tmp_path / f"w0_{tag}.npy")
+    np.save(w0, g[tag + "_w0"])
+    ap.initial_w = w0
+    np.random.seed(c["gseed"])
+    agent = sw.ARSAgent(ep, ap, data_path=DB, seed=c["seed"],
+                        approx_error=None if c["exact"] else c["eps"], sim_thresh=thresh)
+    return agent, ap
+
+
+@pytest.mark.parametrize("tag", "abcdefgh")
+def test_safe_agent_matches_the_reference(tag, tmp_path, capsys):
+    g = _fixture()
+    agent, ap = _agent_for_case(g, tag, tmp_path)
+    assert agent.sim_threshold == g[tag + "_sim_threshold"]
+    est = agent.estimated_param
+    assert np.array_equal([est.l_i, est.m_i, est.k, est.h], g[tag + "_estimated"])
+    per_it = []
+    inner = agent.runOneIteration
+
+    def recorded():
+        r = inner()
+        per_it.append(r)
+        return r
+    agent.runOneIteration = recorded
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        curve = agent.runTraining()
+    counts = np.array([len(r) for r in per_it])
+    assert np.array_equal(counts, g[tag + "_counts"])          # admitted / refused pattern
+    for j, r in enumerate(per_it):
+        _close(r, g[tag + "_returns"][j][:len(r)])
+    _close(curve, g[tag + "_curve"])
+    _close(agent.policy, g[tag + "_policy"])
+    if not ap.V1:
+        _close(agent.mean, g[tag + "_mean"])
+        _close(agent.covariance, g[tag + "_cov"])
+    assert agent.violations == int(g[tag + "_below"])
+    assert capsys.readouterr().out.count("below the threshold") == int(g[tag + "_below"])
+
+
+def _gate_inputs(n, N, seed, v2):
+    rng = np.random.RandomState(seed)
+    m, d = n - 1, 2 * n + 2
+    policy = torch.tensor(rng.uniform(-1, 1, (m, d)), device=DEV)
+    deltas = torch.tensor(2 * rng.rand(N, m, d) - 1, device=DEV)
+    mean = inv_std = None
+    if v2:
+        mean = torch.tensor(rng.uniform(-0.1, 0.1, d), device=DEV)
+        inv_std = torch.tensor(rng.uniform(0.5, 2.0, d), device=DEV)
+    return policy, deltas, mean, inv_std
+
+
+def _host_rule(r, thr):
+    r = r.reshape(-1, 2)
+    return (~(r[:, 0] <= thr) & ~(r[:, 1] <= thr)).astype(np.int32)
+
+
+GATE_SHAPES = [(n, N, form) for n in range(2, 9) for N in (1, 7, 64, 2049) for form in ("auto", "lane")] + \
+              [(3, N, "quad") for N in (1, 7, 64, 2049)] + [(3, 4097, "auto"), (6, 4097, "auto")]
+
+
+@pytest.mark.parametrize("n,N,form", GATE_SHAPES)
+def test_gate_kernel_against_ars_rollouts(n, N, form):
+    H = 60
+    p = SwParams.make(n, 0.9, 1.1, 9.5, 1e-3, (1.0, 0.0), flags=kernel_flags(form))
+    policy, deltas, mean, inv_std = _gate_inputs(n, N, 1000 * n + N, v2=(N % 2 == 1))
+    nu = 0.05
+    ref = kernels.ars_rollouts(p, H, policy, deltas, nu, 0, N, mean=mean, inv_std=inv_std)
+    ref = ref.cpu().numpy()
+    status = torch.zeros(2 * N, dtype=torch.int32, device=DEV)
+    for thr in (float(np.median(ref)), float(ref[0]), float(ref[-1]), np.nan, -np.inf):
+        rets = torch.empty(2 * N, dtype=torch.float64, device=DEV)
+        admit = kernels.ars_gate(p, H, policy, deltas, nu, 0, N, thr, mean=mean, inv_std=inv_std,
+                                 returns=rets, status=status)
+        got = rets.cpu().numpy()
+        assert np.all(np.abs(got - ref) <= 1e-12 * np.maximum(1.0, np.abs(ref)))
+        assert np.array_equal(admit.cpu().numpy(), _host_rule(got, thr))
+    assert int((status != 0).sum()) == 0
+    # a threshold equal to a return refuses its direction
+    a = kernels.ars_gate(p, H, policy, deltas, nu, 0, N, float(ref[0]), mean=mean, inv_std=inv_std).cpu().numpy()
+    assert a[0] == 0
+    # NaN threshold admits everything; the optional outputs may be left out
+    assert kernels.ars_gate(p, H, policy, deltas, nu, 0, N, np.nan, mean=mean, inv_std=inv_std).cpu().numpy().all()
+
+
+def test_gate_on_a_slice_of_the_directions():
+    n, N, H = 3, 40, 50
+    p = SwParams.make(n, 1.0, 1.0, 10.0, 1e-3, (1.0, 0.0))
+    policy, deltas, _, _ = _gate_inputs(n, N, 5, v2=False)
+    ref = kernels.ars_rollouts(p, H, policy, deltas, 0.05, 8, 16).cpu().numpy()
+    rets = torch.empty(32, dtype=torch.float64, device=DEV)
+    admit = kernels.ars_gate(p, H, policy, deltas, 0.05, 8, 16, float(np.median(ref)), returns=rets)
+    assert np.array_equal(rets.cpu().numpy(), ref)
+    assert np.array_equal(admit.cpu().numpy(), _host_rule(ref, float(np.median(ref))))
+
+
+def _pair(tmp_path, N, threshold, safe, record=False, H=100, iters=3):
+    ep = sw.EnvParam("RealWorld", n=3, H=H, l_i=0.8, m_i=1.2, h=1e-3, k=10.2, epsilon=0.001)
+    w0 = str(tmp_path / "w0.npy")
+    np.save(w0, np.random.RandomState(7).uniform(-1, 1, (2, 8)))
+    ap = sw.ARSParam("S", V1=False, n_iter=iters, H=H, N=N, b=N, alpha=0.0075, nu=0.1, safe=safe,
+                     threshold=threshold, initial_w=w0)
+    if safe:
+        return sw.ARSAgent(ep, ap, data_path=DB, seed=4, sim_thresh=Threshold(1, 0.3, 0.001),
+                           record_trajectories=record), ep, ap
+    return sw.ARSAgent(ep, ap, seed=4, record_trajectories=record), ep, ap
+
+
+def test_all_admitted_equals_the_unsafe_agent_bit_for_bit(tmp_path):
+    safe, _, _ = _pair(tmp_path, 64, -1e9, True)
+    plain, _, _ = _pair(tmp_path, 64, -1e9, False)
+    for _ in range(3):
+        np.random.seed(100 + _)
+        st = np.random.get_state()
+        r_safe = safe.runOneIteration()
+        np.random.set_state(st)
+        r_plain = plain.runOneIteration()
+        assert np.array_equal(r_safe, r_plain)
+        assert np.array_equal(safe.last_admitted, np.arange(64))
+    assert np.array_equal(safe.policy, plain.policy)
+    assert np.array_equal(safe.mean, plain.mean)
+
+
+def test_partial_admission_against_the_restatement(tmp_path):
+    N, H = 16, 100
+    agent, ep, ap = _pair(tmp_path, N, 0.0, True, record=True, H=H)
+    # put the simulator threshold in the middle of the first iteration's simulator returns
+    st = np.random.get_state()
+    deltas = 2 * np.random.rand(N, 2, 8) - 1
+    np.random.set_state(st)
+    pol = torch.tensor(agent.policy, device=DEV)
+    sims = kernels.ars_rollouts(agent.p_sim, H, pol, torch.tensor(deltas, device=DEV), ap.nu, 0, N,
+                                mean=agent._mean, inv_std=agent._inv_std).cpu().numpy()
+    agent.sim_threshold = float(np.median(np.minimum(sims[0::2], sims[1::2])) + 1e-9)
+    o = SafeArsOracle(3, (0.8, 1.2, 10.2, 1e-3), (agent.estimated_param.l_i, agent.estimated_param.m_i,
+                                                  agent.estimated_param.k, agent.estimated_param.h),
+                      H, N, N, ap.alpha, ap.nu, False, ap.threshold, agent.sim_threshold, 0,
+                      policy0=agent.policy)
+    o.rng.set_state(np.random.get_state())
+    db0 = agent.database.size
+    partial = 0
+    for _ in range(3):
+        r = agent.runOneIteration()
+        ro = o.iteration()
+        assert np.array_equal(agent.last_admitted, o.last_admitted)
+        partial += 0 < len(o.last_admitted) < N
+        _close(r, ro)
+        _close(agent.policy, o.policy)
+    assert partial >= 1
+    _close(agent.mean, o.mean)
+    _close(agent.covariance, o.covariance)
+    assert agent.violations == o.violations
+    pols = agent.database.policies[db0:]
+    trajs = agent.database.trajectories[db0:]
+    assert len(pols) == len(o.db_policies)
+    for a, b in zip(pols, o.db_policies):
+        _close(a, b)
+    for a, b in zip(trajs, o.db_trajectories):
+        _close(np.array(a), b)
+
+
+def test_all_refused_leaves_the_agent_unchanged(tmp_path):
+    agent, _, _ = _pair(tmp_path, 8, 1e9, True)
+    w0 = np.load(str(tmp_path / "w0.npy"))
+    for _ in range(2):
+        assert agent.runOneIteration() == []
+        assert len(agent.last_admitted) == 0
+        assert np.array_equal(agent.policy, w0)
+        assert np.array_equal(agent.mean, np.zeros(8))
+        assert agent.n_saved_states == 0
+        assert np.array_equal(agent.covariance, np.identity(8))
+
+
+def test_failed_simulator_rollout_raises(tmp_path):
+    agent, _, _ = _pair(tmp_path, 4, 0.0, True)
+    agent.policy = np.full((2, 8), 1e300)          # the simulator state blows up at once
+    with pytest.raises(np.linalg.LinAlgError, match="simulator"):
+        agent.runOneIteration()
