@@ -26,6 +26,8 @@
  *                        surface and the RL-Glue env_step, SwimmerEnvironment.cpp:53-68)
  *   sw_step_residual_f64 Estimator.I: every stored transition re-simulated and compared with its stored next
  *                        state                                       ars/estimator.py:36-62
+ *   sw_step_residual_pop_f64  Estimator.I for a whole CMA-ES generation in one launch (the objective of
+ *                        Estimator.estimate_real_env_param's search)  ars/estimator.py:36-62, :89-110
  *   sw_safe_rollouts_f64 Safe_ARS.isSafe + Safe_ARS.rollout (the one-step simulator look-ahead that gates
  *                        every real step)                            safe_ars/ars.py:111-153
  *
@@ -71,6 +73,9 @@ extern "C" {
 #define SW_STATUS_RANGE 4     /* an angle reached |theta| >= 3e9 rad, outside the range of the
                                  in-kernel sin/cos: outputs are NaN (a simulation that far gone
                                  has ulp(theta) > 4e-7 rad and no meaning left) */
+#define SW_STATUS_PARAM 8     /* sw_step_residual_pop_f64: this candidate's l_i / m_i is non-positive or not
+                                 finite, or its k is not finite (the rule behind SW_ERR_PARAM): its
+                                 partials and value are NaN, the other candidates are unaffected */
 
 /* sw_params.flags: force one of the two rollout kernels (default: chosen from n and n_roll).
  * Both compute the same rollouts; they differ in summation order only (a few ulp per step). */
@@ -122,6 +127,19 @@ int sw_step_f64(const sw_params *p, int64_t n_env, const double *state_in,
 int sw_step_residual_f64(const sw_params *p, int64_t n_env, const double *state, const double *action,
                          const double *next_ref, double *partial, void *stream);
 int64_t sw_step_residual_blocks(int64_t n_env);
+
+/* sw_step_residual_f64 for n_cand parameter sets at once, reading each transition once per workgroup for a group of
+ * candidates.  cand [n_cand][3] holds each candidate's (l_i, m_i, k); n, h, dir_x, dir_y and flags come from `base`
+ * (whose own l_i, m_i, k are validated but not used).  partial [n_cand][sw_step_residual_blocks(n_env)]: row j has
+ * the bits sw_step_residual_f64 writes for candidate j.  value [n_cand] (may be NULL): row j of partial summed in one
+ * fixed order, bit-reproducible -- lane l of a 64-lane wave adds partial[j][l], partial[j][l + 64], ... in turn from
+ * 0.0, then lane sums pair up as in __shfl_down(., 32), (., 16), ..., (., 1).  cand_status [n_cand] (may be NULL):
+ * SW_STATUS_PARAM for a candidate that breaks the parameter rule (NaN partials and value), else 0.
+ * Errors, before any HIP call: NULL pointer SW_ERR_NULL; n_cand < 1, n_cand > 524280 or n_env < 0 SW_ERR_SIZE;
+ * twin model SW_ERR_PARAM.  n_env = 0 writes nothing. */
+int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double *cand, int64_t n_env,
+                             const double *state, const double *action, const double *next_ref, double *partial,
+                             double *value, int32_t *cand_status, void *stream);
 
 int sw_accel_f64(const sw_params *p, int64_t n_env, const double *state,
                  const double *action, double *gdd, double *tdd, void *stream);

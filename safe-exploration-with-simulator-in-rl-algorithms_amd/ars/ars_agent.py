@@ -81,7 +81,7 @@ class ARSAgent(object):
     def __init__(self, real_env_param, agent_param, data_path=None, seed=None,
                  guess_param=None, approx_error=None, sim_thresh=None, *, device=None,
                  process_group=None, record_trajectories=False, full_covariance=True,
-                 top_b=0, rollout_kernel="auto", direct_rccl=None):
+                 top_b=0, rollout_kernel="auto", direct_rccl=None, estimator_options=None):
         self.safe = bool(agent_param.safe)
         if self.safe:
             # the reference reaches `...` (ars_agent.py:64-65) / np.load(None) and fails later
@@ -123,10 +123,10 @@ class ARSAgent(object):
         if self.safe:
             self.database.load(data_path)
             if guess_param is not None:
-                from .estimator import Estimator    # needs the optional `cma` (ImportError without it)
+                from .estimator import Estimator    # CMA-ES: `cma` when it imports, else the built-in search
                 print("Using computed estimation...")
                 self.estimated_param = Estimator(self.database, guess_param,
-                                                 capacity=1).estimate_real_env_param()
+                                                 capacity=1).estimate_real_env_param(**(estimator_options or {}))
             elif approx_error is not None:
                 print("Using approximated estimation...")
                 self.estimated_param = approximate_env_param(real_env_param, approx_error)

@@ -6,16 +6,23 @@ The reference evaluates its objective I(x) by looping over every stored transiti
 (estimator.py:50-55) -- an embarrassingly parallel batch of single physics steps.  Here all
 transitions of all selected trajectories go through ONE launch that steps every transition AND
 compares it with its stored next state (sw_step_residual_f64: the simulated states never reach
-memory); J(x) is one launch of the rollout kernel.  The CMA-ES search around them
-(estimator.py:89-110) is orchestration and needs the `cma` package, which is optional.
+memory); J(x) is one launch of the rollout kernel.
+
+The CMA-ES search around I (estimator.py:89-110) asks for a whole generation of candidates at a time, so
+I_population(X) scores all of them in ONE launch (sw_step_residual_pop_f64: each stored transition is read once for a
+group of candidates) with one host->device copy of the candidates and one device->host read of the values.
+estimate_real_env_param(method="native") runs the built-in NumPy CMA-ES (ars/cmaes.py) on it, one launch per
+generation; method="cma" keeps the optional `cma` package on I(x); "auto" takes `cma` when it imports.
 """
 import dataclasses
+import math
 
 import numpy as np
 import torch
 
 from .. import kernels
 from .._lib import SwParams, require_gpu
+from . import cmaes
 from .parameters import EnvParam
 
 
@@ -37,6 +44,9 @@ class Estimator(object):
         self._cache = None
         self._partial = None
         self._jcache = None
+        self._pop = None
+        self.generations = self.evaluations = 0
+        self.best_f = self.stop_reason = None
 
     def convert_to_env_param(self, x):
         d = dataclasses.asdict(self.guess_param)
@@ -129,11 +139,119 @@ class Estimator(object):
         dists = torch.linalg.vector_norm(per_step, ord=2, dim=0) / H               # [K]
         return float(dists.mean().item())
 
-    def estimate_real_env_param(self):
-        """CMA-ES over I(x) (estimator.py:89-110); needs the optional `cma` package."""
-        import cma
+    def feasible(self, x):
+        """The parameter rule of the library (validate_params): l_i, m_i positive and finite, k finite."""
+        ep = self.convert_to_env_param(x)
+        return (ep.l_i > 0 and ep.m_i > 0 and math.isfinite(ep.l_i) and math.isfinite(ep.m_i)
+                and math.isfinite(ep.k))
+
+    def I_population(self, X):
+        """I(x) for every row of X [lambda, len(unknowns)] -> NumPy [lambda]: one host->device copy of the
+        candidates, ONE launch (sw_step_residual_pop_f64), one device->host read of the values and status.  A row
+        that breaks the parameter rule scores NaN."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if X.shape[1] != len(self.unknowns):
+            raise ValueError(f"expected rows of {len(self.unknowns)} unknowns, got shape {X.shape}")
+        states, nexts, actions, _ = self._batch()
+        eps = [self.convert_to_env_param(x) for x in X]
+        cand = np.array([[ep.l_i, ep.m_i, ep.k] for ep in eps], dtype=np.float64)
+        g = self.guess_param
+        base = SwParams.make(g.n, g.l_i, g.m_i, g.k, g.h, (1.0, 0.0))   # n, h, direction; l_i, m_i, k per candidate
+        lam, nb = cand.shape[0], kernels.step_residual_blocks(states.shape[1])
+        if self._pop is None or self._pop[0].shape[0] != lam or self._pop[1].shape[1] != nb:
+            self._pop = (torch.zeros(lam, dtype=torch.float64, device=self.device),
+                         torch.empty((lam, nb), dtype=torch.float64, device=self.device),
+                         torch.zeros(lam, dtype=torch.int32, device=self.device),
+                         torch.empty((lam, 3), dtype=torch.float64, pin_memory=True))
+        value, partial, status, host = self._pop
+        host.numpy()[:] = cand
+        dcand = host.to(self.device, non_blocking=True)
+        kernels.step_residual_population(base, dcand, states, actions, nexts, partial=partial, value=value,
+                                         status=status)
+        out = torch.cat((value, status.to(torch.float64))).cpu().numpy()
+        f = out[:lam].copy()
+        f[out[lam:] != 0] = np.nan
+        return f
+
+    def _residual_normal(self, u):
+        """Per-transition residuals r = step(x(u)) - stored next state, u = (k l / m, m l^2, k / m): (r.r, J^T J, J^T r)
+        with J by central differences in u (seven step launches, the reductions on the device, one read)."""
+        states, nexts, actions, _ = self._batch()
+        g = self.guess_param
+
+        def r(v):
+            m_i, l_i, k = cmaes.from_constants(v)
+            nxt, _ = kernels.step(SwParams.make(g.n, l_i, m_i, k, g.h, (1.0, 0.0)), states, actions)
+            return (nxt - nexts).reshape(-1)
+
+        r0 = r(u)
+        cols = []
+        for i in range(3):
+            e = np.zeros(3)
+            e[i] = 1e-6 * abs(u[i])
+            cols.append((r(u + e) - r(u - e)) / (2 * e[i]))
+        J = torch.stack(cols)                                                       # [3, d T]
+        out = torch.cat(((r0 @ r0).reshape(1), (J @ J.T).reshape(-1), J @ r0)).cpu().numpy()
+        return out[1:10].reshape(3, 3), out[10:]
+
+    def _residual_cost(self, u):
+        states, nexts, actions, _ = self._batch()
+        g = self.guess_param
+        m_i, l_i, k = cmaes.from_constants(u)
+        nxt, _ = kernels.step(SwParams.make(g.n, l_i, m_i, k, g.h, (1.0, 0.0)), states, actions)
+        return float(((nxt - nexts) ** 2).sum().item())
+
+    def _refine(self, x):
+        """Least-squares refinement of the search's best point in the model's constants (cmaes.refine_least_squares);
+        kept only when I is lower there."""
+        idx = [list(self.unknowns).index(n) for n in ("m_i", "l_i", "k")]
+        u = cmaes.refine_least_squares(self._residual_cost, self._residual_normal,
+                                       cmaes.to_constants(*np.asarray(x)[idx]), feasible=lambda v: bool(np.all(v > 0)))
+        xr = np.empty(3)
+        xr[idx] = cmaes.from_constants(u)
+        fr = self.I_population([xr])[0]
+        if fr < self.best_f:
+            self.best_f = float(fr)
+            return xr
+        return np.asarray(x)
+
+    def estimate_real_env_param(self, method="auto", seed=0, sigma0=1.0, popsize=None, max_generations=None,
+                                refine=True):
+        """CMA-ES over I(x) (estimator.py:89-110), starting at the guess with sigma0 = 1.
+        method "cma": the optional `cma` package on I(x), one launch per candidate; "native": the built-in search
+        (ars/cmaes.py, seeded by `seed`) on I_population, one launch per generation; "auto": "cma" when it imports,
+        else "native".  The native search keeps generations, evaluations, best_f and stop_reason on the estimator and,
+        when the unknowns are m_i, l_i and k and `refine` is set, refines its best point by least squares on the
+        per-transition residuals (cmaes.refine_least_squares, in the constants k l / m, m l^2, k / m)."""
+        if method not in ("auto", "cma", "native"):
+            raise ValueError(f"method must be 'auto', 'cma' or 'native', not {method!r}")
+        if method == "auto":
+            try:
+                import cma
+                method = "cma" if hasattr(cma, "CMAEvolutionStrategy") else "native"
+            except ImportError:
+                method = "native"
+        print("------ Estimating the real world environment parameters ------")
+        print("Extracting the initial guess of real world parameters...")
         d = dataclasses.asdict(self.guess_param)
         x0 = np.array([d[u] for u in self.unknowns], dtype=np.float64)
-        es = cma.CMAEvolutionStrategy(x0, 1).optimize(self.I)
-        est_x, _, _ = es.best.get()
-        return self.convert_to_env_param(est_x)
+        print(f"Initial estimation extracted: {x0}")
+        print("Starting estimation...")
+        if method == "cma":
+            import cma
+            es = cma.CMAEvolutionStrategy(x0, 1).optimize(self.I)
+            est_x, _, _ = es.best.get()
+        else:
+            es = cmaes.minimize(self.I_population, x0, sigma0=sigma0, popsize=popsize, seed=seed,
+                                feasible=self.feasible, max_generations=max_generations)
+            est_x, self.best_f = es.best_x, es.best_f
+            self.generations, self.evaluations, self.stop_reason = es.generations, es.evaluations, es.stop_reason
+            print(f"native CMA-ES: best f {es.best_f:.6e} at {est_x}, {es.generations} generations, "
+                  f"{es.evaluations} evaluations, stop: {es.stop_reason}")
+            if refine and sorted(self.unknowns) == ["k", "l_i", "m_i"] and np.isfinite(es.best_f):
+                est_x = self._refine(est_x)
+                print(f"refined: f {self.best_f:.6e} at {est_x}")
+        print("Estimation finished")
+        env_param = self.convert_to_env_param(est_x)
+        print(f"Estimated parameters: {env_param}")
+        return env_param

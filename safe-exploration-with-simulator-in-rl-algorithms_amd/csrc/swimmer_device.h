@@ -50,6 +50,24 @@ struct Consts {
     double c12;      // 12 / (m l^2)
 };
 
+// The constants of one parameter set.  The host (make_consts, from sw_params) and the population residual kernel
+// (one parameter set per candidate, from a device array) both derive them here, so that both get the same bits.
+__host__ __device__ inline Consts consts_of(int n, double l_i, double m_i, double k, double h, double dirx,
+                                            double diry)
+{
+    Consts c;
+    c.l = l_i;
+    c.h = h;
+    c.dirx = dirx;
+    c.diry = diry;
+    c.kl_nm = k * l_i / ((double)n * m_i);
+    c.h_kl_nm = c.h * c.kl_nm;
+    c.six_k_m = 6.0 * k / m_i;
+    c.kl_m = k * l_i / m_i;
+    c.c12 = 12.0 / (m_i * l_i * l_i);
+    return c;
+}
+
 // ---- compile-time chain weights ------------------------------------------------------
 template <int N> __host__ __device__ constexpr double wbar(int k1) { return (N - k1 + 0.5) / N; }
 template <int N> __host__ __device__ constexpr double vel_w(int j1, int k1)

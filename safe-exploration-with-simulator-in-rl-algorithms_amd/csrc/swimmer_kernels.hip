@@ -109,22 +109,14 @@ constexpr int kUpdBlock = 256;        // update kernel: threads per workgroup up
 constexpr int kUpdBlockWide = 1024;   // ... and beyond (a thread's share of the directions stays short)
 constexpr int32_t kUpdWideFrom = 1025;
 constexpr int64_t kStepStreamBytes = (int64_t)256 << 20;   // beyond the Infinity Cache: nontemporal accesses
+constexpr int kPopGroup = 8;          // sw_step_residual_pop_f64: candidates per workgroup, ...
+constexpr int64_t kPopMaxCandidates = (int64_t)65535 * kPopGroup;   // ... and at most 65535 groups (grid.y)
 constexpr double kHalfPi = 1.57079632679489661923;  // math.pi / 2 (remy_swimmer_env.py:65)
 constexpr double kTwinStart = 0.001;                // SwimmerEnvironment.cpp:41
 
 sw::Consts make_consts(const sw_params *p)
 {
-    sw::Consts c;
-    c.l = p->l_i;
-    c.h = p->h;
-    c.dirx = p->dir_x;
-    c.diry = p->dir_y;
-    c.kl_nm = p->k * p->l_i / ((double)p->n * p->m_i);
-    c.h_kl_nm = c.h * c.kl_nm;
-    c.six_k_m = 6.0 * p->k / p->m_i;
-    c.kl_m = p->k * p->l_i / p->m_i;
-    c.c12 = 12.0 / (p->m_i * p->l_i * p->l_i);
-    return c;
+    return sw::consts_of(p->n, p->l_i, p->m_i, p->k, p->h, p->dir_x, p->dir_y);
 }
 
 sw::TwinConsts make_twin_consts(const sw_params *p)
@@ -270,6 +262,106 @@ step_residual_kernel(sw::Consts C, int64_t n_env, const double *__restrict__ sin
         for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[w];
         partial[blockIdx.x] = t;
     }
+}
+
+// The same objective for a POPULATION of parameter sets (the CMA-ES generation of the estimator's search): each
+// workgroup reads its 256 transitions ONCE into registers and steps a copy of every state for each candidate of its
+// group (blockIdx.y: candidates [y * kPopGroup, ...)).  Per candidate everything is step_residual_kernel's: the same
+// partition, the same consts (sw::consts_of, here from the candidate's l_i, m_i, k), euler_step, the same FMA chain, the
+// same lane tree and wave order -- partial[j][b] has the bits step_residual_kernel gives for candidate j.  A candidate
+// that breaks validate_params' rule gets NaN partials and SW_STATUS_PARAM; its neighbours do not notice.
+template <int N, bool NT>
+__global__ void __launch_bounds__(kStepBlock)
+step_residual_pop_kernel(sw::Consts base, int64_t n_cand, const double *__restrict__ cand, int64_t n_env,
+                         const double *__restrict__ sin_, const double *__restrict__ act,
+                         const double *__restrict__ next_ref, double *__restrict__ partial,
+                         int32_t *__restrict__ cand_status)
+{
+    constexpr int M = N - 1;
+    __shared__ sw::Consts cc[kPopGroup];
+    __shared__ int cok[kPopGroup];
+    __shared__ double wsum[kPopGroup][kStepBlock / kWave];
+    const int64_t j0 = (int64_t)blockIdx.y * kPopGroup;
+    const int nc = (int)(n_cand - j0 < kPopGroup ? n_cand - j0 : kPopGroup);
+    if ((int)threadIdx.x < nc) {
+        const double *x = cand + (j0 + threadIdx.x) * 3;   // [l_i, m_i, k]
+        const double l = x[0], m = x[1], k = x[2];
+        const bool ok = l > 0.0 && m > 0.0 && isfinite(l) && isfinite(m) && isfinite(k);
+        cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
+        cok[threadIdx.x] = ok;
+        if (cand_status && blockIdx.x == 0) cand_status[j0 + threadIdx.x] = ok ? SW_STATUS_OK : SW_STATUS_PARAM;
+    }
+    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    const bool live = e < n_env;
+    double gdx = 0.0, gdy = 0.0, th[N], thd[N], u[M], rx = 0.0, ry = 0.0, rth[N], rthd[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) th[i] = thd[i] = rth[i] = rthd[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) u[i] = 0.0;
+    if (live) {
+        gdx = SW_LD(&sin_[e]);
+        gdy = SW_LD(&sin_[n_env + e]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
+            thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
+        }
+#pragma unroll
+        for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
+        rx = SW_LD(&next_ref[e]);
+        ry = SW_LD(&next_ref[n_env + e]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            rth[i] = SW_LD(&next_ref[(int64_t)(2 + 2 * i) * n_env + e]);
+            rthd[i] = SW_LD(&next_ref[(int64_t)(3 + 2 * i) * n_env + e]);
+        }
+    }
+    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+    __syncthreads();
+#pragma unroll 1
+    for (int c = 0; c < nc; ++c) {
+        double dist = 0.0;
+        if (live) {
+            double x = gdx, y = gdy, t[N], td[N], r;
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                t[i] = th[i];
+                td[i] = thd[i];
+            }
+            (void)sw::euler_step<N>(cc[c], x, y, t, td, u, r);
+            double q = (x - rx) * (x - rx);
+            q = __builtin_fma(y - ry, y - ry, q);
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                q = __builtin_fma(t[i] - rth[i], t[i] - rth[i], q);
+                q = __builtin_fma(td[i] - rthd[i], td[i] - rthd[i], q);
+            }
+            dist = (in_range && cok[c]) ? sqrt(q) : __builtin_nan("");
+        }
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
+        if (threadIdx.x % kWave == 0) wsum[c][threadIdx.x / kWave] = dist;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nc) {
+        double t = wsum[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
+        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// value[j] = the sum of row j of partial [n_cand][nb] in ONE fixed order: lane l adds b = l, l + 64, l + 128, ... in
+// turn (starting from 0.0), then the 64 lane sums go through the shuffle tree.  One wave per candidate.
+__global__ void __launch_bounds__(kWave)
+residual_rows_sum_kernel(int64_t nb, const double *__restrict__ partial, double *__restrict__ value)
+{
+    const double *row = partial + (int64_t)blockIdx.x * nb;
+    double t = 0.0;
+    for (int64_t b = threadIdx.x; b < nb; b += kWave) t += row[b];
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) t += __shfl_down(t, off, kWave);
+    if (threadIdx.x == 0) value[blockIdx.x] = t;
 }
 
 template <int N, bool TWIN>
@@ -2059,6 +2151,39 @@ int sw_step_residual_f64(const sw_params *p, int64_t n_env, const double *state,
     } else {
         SW_DISPATCH_N(p->n, hipLaunchKernelGGL((step_residual_kernel<NN, false>), dim3(grid), dim3(kStepBlock), 0,
                                                (hipStream_t)stream, C, n_env, state, action, next_ref, partial));
+    }
+    return launch_status();
+}
+
+int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double *cand, int64_t n_env,
+                             const double *state, const double *action, const double *next_ref, double *partial,
+                             double *value, int32_t *cand_status, void *stream)
+{
+    int rc = check_params(base);
+    if (rc) return rc;
+    if (!cand || !state || !action || !next_ref || !partial) return SW_ERR_NULL;
+    if (n_cand < 1 || n_cand > kPopMaxCandidates || n_env < 0) return SW_ERR_SIZE;
+    if (is_twin(base)) return SW_ERR_PARAM;
+    if (n_env == 0) return SW_OK;
+    const sw::Consts C = make_consts(base);    // h and the direction; l_i, m_i, k come from each candidate
+    const int64_t nb = (n_env + kStepBlock - 1) / kStepBlock;
+    const dim3 grid((unsigned)nb, (unsigned)((n_cand + kPopGroup - 1) / kPopGroup));
+    const int d = 2 * base->n + 2;
+    const bool nt = n_env * (int64_t)(8 * (2 * d + base->n)) > kStepStreamBytes;   // sw_step_residual_f64's switch
+    if (nt) {
+        SW_DISPATCH_N(base->n, hipLaunchKernelGGL((step_residual_pop_kernel<NN, true>), grid, dim3(kStepBlock), 0,
+                                                  (hipStream_t)stream, C, n_cand, cand, n_env, state, action,
+                                                  next_ref, partial, cand_status));
+    } else {
+        SW_DISPATCH_N(base->n, hipLaunchKernelGGL((step_residual_pop_kernel<NN, false>), grid, dim3(kStepBlock), 0,
+                                                  (hipStream_t)stream, C, n_cand, cand, n_env, state, action,
+                                                  next_ref, partial, cand_status));
+    }
+    if (value) {
+        rc = launch_status();
+        if (rc) return rc;
+        hipLaunchKernelGGL(residual_rows_sum_kernel, dim3((unsigned)n_cand), dim3(kWave), 0, (hipStream_t)stream, nb,
+                           partial, value);
     }
     return launch_status();
 }

@@ -64,6 +64,39 @@ def step_residual(p: SwParams, state, action, next_ref, partial=None):
     return partial
 
 
+def step_residual_population(p_base: SwParams, cand, state, action, next_ref, partial=None, value=None, status=None):
+    """step_residual for a whole population of parameter sets in one launch (sw_step_residual_pop_f64): cand
+    [n_cand, 3] float64 holds each candidate's (l_i, m_i, k) on the device; n, h and the direction come from p_base.
+    Returns (value [n_cand], partial [n_cand, step_residual_blocks(T)], status [n_cand] int32): partial row j has the
+    bits step_residual gives for candidate j, value[j] is its fixed-order sum, status[j] is SW_STATUS_PARAM (8) for
+    a candidate with non-positive / non-finite l_i, m_i or non-finite k (NaN partials and value), else 0."""
+    require_gpu()
+    T = state.shape[1]
+    _want(state, "state", (p_base.d, T))
+    _want(action, "action", (p_base.m, T))
+    _want(next_ref, "next_ref", (p_base.d, T))
+    if cand.dim() != 2 or cand.shape[0] < 1:
+        raise _lib.SwimmerHipError(f"cand: expected float64 tensor of shape (n_cand, 3), got {tuple(cand.shape)}")
+    n_cand = cand.shape[0]
+    _want(cand, "cand", (n_cand, 3))
+    if not cand.is_contiguous():
+        raise _lib.SwimmerHipError("cand: expected a contiguous tensor")
+    nb = int(load().sw_step_residual_blocks(T))
+    partial = _f64((n_cand, nb), state.device) if partial is None else _want(partial, "partial", (n_cand, nb))
+    if value is None:   # zeros: with T = 0 the library writes nothing and I is 0
+        value = torch.zeros((n_cand,), dtype=torch.float64, device=state.device)
+    else:
+        _want(value, "value", (n_cand,))
+    if status is None:
+        status = torch.zeros((n_cand,), dtype=torch.int32, device=state.device)
+    elif status.dtype != torch.int32 or tuple(status.shape) != (n_cand,):
+        raise _lib.SwimmerHipError(f"status: expected int32 tensor of shape ({n_cand},)")
+    check(load().sw_step_residual_pop_f64(ctypes.byref(p_base), n_cand, ptr(cand), T, ptr(state), ptr(action),
+                                          ptr(next_ref), ptr(partial), ptr(value), ptr(status), stream_ptr()),
+          "sw_step_residual_pop_f64")
+    return value, partial, status
+
+
 class StepPlan(object):
     """A pre-bound sw_step_f64 launch: all argument conversion is done once, `launch()` is a
     single foreign call (the per-launch Python overhead of `step()` is larger than the 8192-env
