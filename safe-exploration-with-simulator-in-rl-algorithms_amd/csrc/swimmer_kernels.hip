@@ -23,6 +23,8 @@
 //   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound
 //   + the native ARS iteration pipeline (sw_ars_pipeline_*: copy stream, progress flag, 4-slot
 //     buffer ring; the covariance pass rides along in the next rollout launch, SideJob)
+// Which of the four rollout forms a launch takes, and with which grid, is decided in ONE place,
+// plan_rollouts(); run-time flags and n become template arguments through with_bools() / with_n<LO, HI>().
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1901,118 +1903,92 @@ __global__ void __launch_bounds__(256) issue_probe_kernel(int32_t trips, int32_t
 }
 
 // ---- dispatch on the segment count -------------------------------------------------
-#define SW_DISPATCH_N(n, CALL)                 \
-    switch (n) {                               \
-    case 2: { constexpr int NN = 2; CALL; } break; \
-    case 3: { constexpr int NN = 3; CALL; } break; \
-    case 4: { constexpr int NN = 4; CALL; } break; \
-    case 5: { constexpr int NN = 5; CALL; } break; \
-    case 6: { constexpr int NN = 6; CALL; } break; \
-    case 7: { constexpr int NN = 7; CALL; } break; \
-    case 8: { constexpr int NN = 8; CALL; } break; \
-    default: return SW_ERR_SEGMENTS;           \
-    }
-
-#define SW_DISPATCH_QUAD(ARS, HAS_TRAJ, HAS_MOM, STREAM, ...)                                   \
-    do {                                                                                         \
-        if (HAS_TRAJ) {                                                                          \
-            if (HAS_MOM)                                                                         \
-                hipLaunchKernelGGL((rollout_quad3_kernel<ARS, true, true>), dim3(grid),          \
-                                   dim3(kRollBlock), 0, STREAM, __VA_ARGS__);                    \
-            else                                                                                 \
-                hipLaunchKernelGGL((rollout_quad3_kernel<ARS, true, false>), dim3(grid),         \
-                                   dim3(kRollBlock), 0, STREAM, __VA_ARGS__);                    \
-        } else {                                                                                 \
-            if (HAS_MOM)                                                                         \
-                hipLaunchKernelGGL((rollout_quad3_kernel<ARS, false, true>), dim3(grid),         \
-                                   dim3(kRollBlock), 0, STREAM, __VA_ARGS__);                    \
-            else                                                                                 \
-                hipLaunchKernelGGL((rollout_quad3_kernel<ARS, false, false>), dim3(grid),        \
-                                   dim3(kRollBlock), 0, STREAM, __VA_ARGS__);                    \
-        }                                                                                        \
-    } while (0)
-
-#define SW_DISPATCH_OCT(ARS, HAS_TRAJ, HAS_MOM, STREAM, ...)                                    \
-    do {                                                                                         \
-        if (HAS_TRAJ) {                                                                          \
-            if (HAS_MOM)                                                                         \
-                hipLaunchKernelGGL((rollout_oct3_kernel<ARS, true, true>), dim3(grid),           \
-                                   dim3(kOctBlock), 0, STREAM, __VA_ARGS__);                     \
-            else                                                                                 \
-                hipLaunchKernelGGL((rollout_oct3_kernel<ARS, true, false>), dim3(grid),          \
-                                   dim3(kOctBlock), 0, STREAM, __VA_ARGS__);                     \
-        } else {                                                                                 \
-            if (HAS_MOM)                                                                         \
-                hipLaunchKernelGGL((rollout_oct3_kernel<ARS, false, true>), dim3(grid),          \
-                                   dim3(kOctBlock), 0, STREAM, __VA_ARGS__);                     \
-            else                                                                                 \
-                hipLaunchKernelGGL((rollout_oct3_kernel<ARS, false, false>), dim3(grid),         \
-                                   dim3(kOctBlock), 0, STREAM, __VA_ARGS__);                     \
-        }                                                                                        \
-    } while (0)
-
-// Kernel choice for rollouts: the quad (segment-per-lane) kernel while it still finds idle
-// SIMDs, the lane-per-rollout kernel beyond; sw_params.flags can force either.
-bool use_quad3(const sw_params *p, int64_t n_roll, int32_t H, bool with_traj)
+// Run-time values to template arguments.  f is a generic lambda that takes them BY VALUE as
+// std::integral_constant, so `N.value` / `TRAJ.value` are constant expressions inside it.
+template <class F> void with_bools(F &&f) { f(); }
+template <class F, class... Rest> void with_bools(F &&f, bool b, Rest... rest)
 {
-    if (p->n != 3 || is_twin(p)) return false;   // segment-per-lane kernels: Gym model only
-    if (p->flags & SW_FLAG_ROLLOUT_LANE) return false;
-    // the quad kernel addresses the trajectory buffer with 32-bit byte offsets
-    if (with_traj && (int64_t)H * 8 * n_roll * 8 >= ((int64_t)1 << 32)) return false;
-    if (n_roll >= ((int64_t)1 << 25)) return false;
-    if (p->flags & SW_FLAG_ROLLOUT_QUAD) return true;
-    return n_roll <= kQuadMaxRollouts;
+    if (b)
+        with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else
+        with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
 }
 
-// n = 3 with lane roles (two mirror quads per rollout, swimmer_oct3.h): 8 rollouts per wave, so it
-// keeps one wave per SIMD up to 8192 rollouts; beyond that the quad kernel (16 per wave) takes over.
-// SWIMMER_N3_KERNEL=quad|oct overrides the default (measurement knob).
+// f(N, bools...) for n in the closed range LO..HI -- the only values a kernel is instantiated for;
+// false (the caller's SW_ERR_SEGMENTS) when n is outside it.
+template <int LO, int HI, class F, class... Bools> bool with_n(int n, F &&f, Bools... bools)
+{
+    if constexpr (LO > HI) {
+        return false;
+    } else {
+        if (n != LO) return with_n<LO + 1, HI>(n, f, bools...);
+        with_bools([&](auto... cs) { f(std::integral_constant<int, LO>{}, cs...); }, bools...);
+        return true;
+    }
+}
+
+// The four forms of a rollout launch (file header), and the one place that chooses between them.
+enum class Form { Oct3, Quad3, Row, Lane };
+constexpr Form kForms[] = {Form::Oct3, Form::Quad3, Form::Row, Form::Lane};
 constexpr int64_t kOctMaxRollouts = 8192;
-bool use_oct3(const sw_params *p, int64_t n_roll, int32_t H, bool with_traj)
+
+constexpr int form_block(Form f)
+{
+    return f == Form::Oct3 ? kOctBlock : f == Form::Row ? kRowBlock : kRollBlock;
+}
+
+// Workgroup size of the covariance pass that a launch of form f leaves owed: the pass rides along in a
+// launch of the same form, or is flushed with that form's workgroups.  The lane kernel carries no side
+// job, so its pass is always the flushed one, with the standalone pass's kMomBlock.
+constexpr int owed_cov_block(Form f) { return f == Form::Lane ? kMomBlock : form_block(f); }
+
+struct RolloutPlan {
+    Form form;
+    int block;                 // threads per workgroup
+    unsigned rollout_blocks;   // workgroups that run rollouts (a side job's come behind them)
+    bool carries_side;         // the form's kernels take a SideJob
+};
+
+// Kernel choice for rollouts: a segment-per-lane kernel while it still finds idle SIMDs, the
+// lane-per-rollout kernel beyond; sw_params.flags can force either.
+//  * n = 3 with lane roles (two mirror quads per rollout, swimmer_oct3.h): 8 rollouts per wave, so it
+//    keeps one wave per SIMD up to 8192 rollouts; beyond that the quad kernel (16 per wave) takes over.
+//    SWIMMER_N3_KERNEL=quad|oct overrides the default (measurement knob).  allow_quad = false: the
+//    caller has no quad kernel (safe rollouts).
+//  * n = 4..8: the row kernel.
+RolloutPlan plan_rollouts(const sw_params *p, int64_t n_roll, int32_t H, bool with_traj, bool allow_quad = true)
 {
     static const char *env = getenv("SWIMMER_N3_KERNEL");
-    const bool want = env ? (env[0] == 'o') : SW_N3_DEFAULT_OCT;
-    return want && n_roll <= kOctMaxRollouts && use_quad3(p, n_roll, H, with_traj);
-}
-
-// n = 4..8: the row (segment-per-lane) kernel while it still finds idle SIMDs.
-bool use_row(const sw_params *p, int64_t n_roll, int32_t H, bool with_traj)
-{
-    if (p->n < 4 || is_twin(p)) return false;
-    if (p->flags & SW_FLAG_ROLLOUT_LANE) return false;
-    if (with_traj && (int64_t)H * (2 * p->n + 2) * n_roll * 8 >= ((int64_t)1 << 32) - 256) return false;
-    if (n_roll >= ((int64_t)1 << 24)) return false;
-    if (p->flags & SW_FLAG_ROLLOUT_QUAD) return true;
-    return n_roll <= kRowMaxRollouts;
-}
-
-#define SW_LAUNCH_ROW(NN, ARS, HAS_TRAJ, HAS_MOM, STREAM, ...)                                  \
-    do {                                                                                         \
-        if (HAS_TRAJ) {                                                                          \
-            if (HAS_MOM)                                                                         \
-                hipLaunchKernelGGL((rollout_row_kernel<NN, ARS, true, true>), dim3(grid),        \
-                                   dim3(kRowBlock), 0, STREAM, __VA_ARGS__);                     \
-            else                                                                                 \
-                hipLaunchKernelGGL((rollout_row_kernel<NN, ARS, true, false>), dim3(grid),       \
-                                   dim3(kRowBlock), 0, STREAM, __VA_ARGS__);                     \
-        } else {                                                                                 \
-            if (HAS_MOM)                                                                         \
-                hipLaunchKernelGGL((rollout_row_kernel<NN, ARS, false, true>), dim3(grid),       \
-                                   dim3(kRowBlock), 0, STREAM, __VA_ARGS__);                     \
-            else                                                                                 \
-                hipLaunchKernelGGL((rollout_row_kernel<NN, ARS, false, false>), dim3(grid),      \
-                                   dim3(kRowBlock), 0, STREAM, __VA_ARGS__);                     \
-        }                                                                                        \
-    } while (0)
-
-#define SW_DISPATCH_ROW(n, ARS, HAS_TRAJ, HAS_MOM, STREAM, ...)                                 \
-    switch (n) {                                                                                 \
-    case 4: SW_LAUNCH_ROW(4, ARS, HAS_TRAJ, HAS_MOM, STREAM, __VA_ARGS__); break;                \
-    case 5: SW_LAUNCH_ROW(5, ARS, HAS_TRAJ, HAS_MOM, STREAM, __VA_ARGS__); break;                \
-    case 6: SW_LAUNCH_ROW(6, ARS, HAS_TRAJ, HAS_MOM, STREAM, __VA_ARGS__); break;                \
-    case 7: SW_LAUNCH_ROW(7, ARS, HAS_TRAJ, HAS_MOM, STREAM, __VA_ARGS__); break;                \
-    default: SW_LAUNCH_ROW(8, ARS, HAS_TRAJ, HAS_MOM, STREAM, __VA_ARGS__); break;               \
+    const bool want_oct = env ? (env[0] == 'o') : SW_N3_DEFAULT_OCT;
+    const bool uncapped = (p->flags & SW_FLAG_ROLLOUT_QUAD) != 0;
+    Form form = Form::Lane;
+    // segment-per-lane kernels: Gym model only
+    if (!is_twin(p) && !(p->flags & SW_FLAG_ROLLOUT_LANE)) {
+        if (p->n == 3) {
+            // the quad and mirror-quad kernels address the trajectory buffer with 32-bit byte offsets
+            const bool fits = !(with_traj && (int64_t)H * 8 * n_roll * 8 >= ((int64_t)1 << 32)) &&
+                              n_roll < ((int64_t)1 << 25) && (uncapped || n_roll <= kQuadMaxRollouts);
+            if (fits && want_oct && n_roll <= kOctMaxRollouts)
+                form = Form::Oct3;
+            else if (fits && allow_quad)
+                form = Form::Quad3;
+        } else if (p->n >= 4) {
+            const bool fits =
+                !(with_traj && (int64_t)H * (2 * p->n + 2) * n_roll * 8 >= ((int64_t)1 << 32) - 256) &&
+                n_roll < ((int64_t)1 << 24) && (uncapped || n_roll <= kRowMaxRollouts);
+            if (fits) form = Form::Row;
+        }
     }
+    const int per_block = form == Form::Lane ? kRollBlock : kMomGroup;   // rollouts per workgroup
+    return RolloutPlan{form, form_block(form), (unsigned)((n_roll + per_block - 1) / per_block), form != Form::Lane};
+}
+
+// Batches beyond the Infinity Cache stream through HBM: the step kernels' NT (nontemporal) forms.
+bool streams_through_hbm(const sw_params *p, int64_t n_env)
+{
+    const int d = 2 * p->n + 2;
+    return n_env * (int64_t)(8 * (2 * d + p->n)) > kStepStreamBytes;
+}
 
 int launch_status()
 {
@@ -2037,6 +2013,67 @@ unsigned side_attach_cov(SideJob &sj, unsigned roll_blocks, int block, int sj_D)
     static const char *nap_env = getenv("SWIMMER_COV_NAP");   // measurement knob
     sj.cov_nap = nap_env ? atoi(nap_env) : 0;
     return sj.cov_tiles;
+}
+
+// What the rollout kernels take besides the model and the batch.  Plain rollouts (sw_rollout_f64): one
+// policy per rollout, no deltas.  ARS rollouts: one policy, +-nu deltas[dir_begin + i], no state0 /
+// final_state.
+struct RolloutArgs {
+    const double *policies, *deltas;
+    int64_t dir_begin;
+    double nu;
+    const double *mean, *inv_std, *state0;
+    double *returns, *traj, *final_state, *moments;
+    int32_t *status;
+};
+
+// The one rollout launcher: `plan` says which kernel and which grid.  side: what the launch carries besides
+// the rollouts (pipeline only; the lane form cannot take it, RolloutPlan::carries_side).  The public entry
+// points have validated p and the sizes, and cleared stale errors, already.
+int launch_rollouts(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H,
+                    const RolloutArgs &a, hipStream_t stream, const SideJob *side = nullptr)
+{
+    if (!a.policies || !a.returns) return SW_ERR_NULL;
+    if ((a.mean == nullptr) != (a.inv_std == nullptr)) return SW_ERR_NULL;
+    const sw::Consts C = make_consts(p);
+    const bool has_traj = a.traj != nullptr, has_mom = a.moments != nullptr;
+    auto segment_per_lane = [&](auto *kernel) {
+        SideJob sj = side ? *side : kNoSide;
+        unsigned grid = plan.rollout_blocks;
+        grid += side_attach_cov(sj, grid, plan.block, 2 * p->n + 2);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(plan.block), 0, stream, C, n_roll, H, a.policies, a.deltas,
+                           a.dir_begin, a.nu, a.mean, a.inv_std, a.state0, a.returns, a.traj, a.final_state,
+                           a.moments, a.status, sj);
+    };
+    bool known_n = true;
+    switch (plan.form) {
+    case Form::Oct3:
+        with_bools([&](auto ARS, auto TRAJ, auto MOM) {
+            segment_per_lane(rollout_oct3_kernel<ARS.value, TRAJ.value, MOM.value>);
+        }, ars, has_traj, has_mom);
+        break;
+    case Form::Quad3:
+        with_bools([&](auto ARS, auto TRAJ, auto MOM) {
+            segment_per_lane(rollout_quad3_kernel<ARS.value, TRAJ.value, MOM.value>);
+        }, ars, has_traj, has_mom);
+        break;
+    case Form::Row:
+        known_n = with_n<4, 8>(p->n, [&](auto N, auto ARS, auto TRAJ, auto MOM) {
+            segment_per_lane(rollout_row_kernel<N.value, ARS.value, TRAJ.value, MOM.value>);
+        }, ars, has_traj, has_mom);
+        break;
+    case Form::Lane: {
+        const sw::TwinConsts T = make_twin_consts(p);
+        known_n = with_n<2, 8>(p->n, [&](auto N, auto ARS, auto TWIN) {
+            hipLaunchKernelGGL((rollout_kernel<N.value, ARS.value, TWIN.value>), dim3(plan.rollout_blocks),
+                               dim3(plan.block), 0, stream, C, T, n_roll, H, a.policies, a.deltas, a.dir_begin,
+                               a.nu, a.mean, a.inv_std, a.state0, a.returns, a.traj, a.final_state, a.moments,
+                               a.status);
+        }, ars, is_twin(p));
+        break;
+    }
+    }
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 }  // namespace
@@ -2112,24 +2149,18 @@ int sw_step_f64(const sw_params *p, int64_t n_env, const double *state_in, const
     const sw::Consts C = make_consts(p);
     const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
     const sw::TwinConsts T = make_twin_consts(p);
-    const int d = 2 * p->n + 2;
-    bool nt = n_env * (int64_t)(8 * (2 * d + p->n)) > kStepStreamBytes;
+    bool nt = streams_through_hbm(p, n_env);
     static const char *nt_env = getenv("SWIMMER_STEP_NT");   // measurement knob: "0" / "1" force it
     if (nt_env && (nt_env[0] == '0' || nt_env[0] == '1')) nt = nt_env[0] == '1';
-    if (is_twin(p)) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((step_kernel<NN, true, false>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, T, n_env, state_in, action,
-                                               state_out, reward, status));
-    } else if (nt) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((step_kernel<NN, false, true>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, T, n_env, state_in, action,
-                                               state_out, reward, status));
-    } else {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((step_kernel<NN, false, false>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, T, n_env, state_in, action,
-                                               state_out, reward, status));
-    }
-    return launch_status();
+    auto launch = [&](auto *kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kStepBlock), 0, (hipStream_t)stream, C, T, n_env, state_in,
+                           action, state_out, reward, status);
+    };
+    // (the twin model has no nontemporal form)
+    const bool known_n =
+        is_twin(p) ? with_n<2, 8>(p->n, [&](auto N) { launch(step_kernel<N.value, true, false>); })
+                   : with_n<2, 8>(p->n, [&](auto N, auto NT) { launch(step_kernel<N.value, false, NT.value>); }, nt);
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 int sw_step_residual_f64(const sw_params *p, int64_t n_env, const double *state, const double *action,
@@ -2143,16 +2174,11 @@ int sw_step_residual_f64(const sw_params *p, int64_t n_env, const double *state,
     if (!state || !action || !next_ref || !partial) return SW_ERR_NULL;
     const sw::Consts C = make_consts(p);
     const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
-    const int d = 2 * p->n + 2;
-    const bool nt = n_env * (int64_t)(8 * (2 * d + p->n)) > kStepStreamBytes;
-    if (nt) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((step_residual_kernel<NN, true>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, n_env, state, action, next_ref, partial));
-    } else {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((step_residual_kernel<NN, false>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, n_env, state, action, next_ref, partial));
-    }
-    return launch_status();
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto NT) {
+        hipLaunchKernelGGL((step_residual_kernel<N.value, NT.value>), dim3(grid), dim3(kStepBlock), 0,
+                           (hipStream_t)stream, C, n_env, state, action, next_ref, partial);
+    }, streams_through_hbm(p, n_env));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double *cand, int64_t n_env,
@@ -2168,17 +2194,12 @@ int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double
     const sw::Consts C = make_consts(base);    // h and the direction; l_i, m_i, k come from each candidate
     const int64_t nb = (n_env + kStepBlock - 1) / kStepBlock;
     const dim3 grid((unsigned)nb, (unsigned)((n_cand + kPopGroup - 1) / kPopGroup));
-    const int d = 2 * base->n + 2;
-    const bool nt = n_env * (int64_t)(8 * (2 * d + base->n)) > kStepStreamBytes;   // sw_step_residual_f64's switch
-    if (nt) {
-        SW_DISPATCH_N(base->n, hipLaunchKernelGGL((step_residual_pop_kernel<NN, true>), grid, dim3(kStepBlock), 0,
-                                                  (hipStream_t)stream, C, n_cand, cand, n_env, state, action,
-                                                  next_ref, partial, cand_status));
-    } else {
-        SW_DISPATCH_N(base->n, hipLaunchKernelGGL((step_residual_pop_kernel<NN, false>), grid, dim3(kStepBlock), 0,
-                                                  (hipStream_t)stream, C, n_cand, cand, n_env, state, action,
-                                                  next_ref, partial, cand_status));
-    }
+    const bool known_n = with_n<2, 8>(base->n, [&](auto N, auto NT) {
+        hipLaunchKernelGGL((step_residual_pop_kernel<N.value, NT.value>), grid, dim3(kStepBlock), 0,
+                           (hipStream_t)stream, C, n_cand, cand, n_env, state, action, next_ref, partial,
+                           cand_status);
+    }, streams_through_hbm(base, n_env));
+    if (!known_n) return SW_ERR_SEGMENTS;
     if (value) {
         rc = launch_status();
         if (rc) return rc;
@@ -2201,14 +2222,11 @@ int sw_accel_f64(const sw_params *p, int64_t n_env, const double *state, const d
     const sw::Consts C = make_consts(p);
     const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
     const sw::TwinConsts T = make_twin_consts(p);
-    if (is_twin(p)) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((accel_kernel<NN, true>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, T, n_env, state, action, gdd, tdd));
-    } else {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((accel_kernel<NN, false>), dim3(grid), dim3(kStepBlock), 0,
-                                               (hipStream_t)stream, C, T, n_env, state, action, gdd, tdd));
-    }
-    return launch_status();
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
+        hipLaunchKernelGGL((accel_kernel<N.value, TWIN.value>), dim3(grid), dim3(kStepBlock), 0,
+                           (hipStream_t)stream, C, T, n_env, state, action, gdd, tdd);
+    }, is_twin(p));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 int sw_rollout_f64(const sw_params *p, int64_t n_roll, int32_t H, const double *policies,
@@ -2220,48 +2238,10 @@ int sw_rollout_f64(const sw_params *p, int64_t n_roll, int32_t H, const double *
     if (rc) return rc;
     if (n_roll < 0 || H < 0) return SW_ERR_SIZE;
     if (n_roll == 0) return SW_OK;
-    if (!policies || !returns) return SW_ERR_NULL;
-    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
-    const sw::Consts C = make_consts(p);
-    if (use_oct3(p, n_roll, H, traj != nullptr)) {
-        const unsigned grid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-        SW_DISPATCH_OCT(false, traj != nullptr, moments != nullptr,
-                        (hipStream_t)stream, C, n_roll, H, policies, (const double *)nullptr,
-                        (int64_t)0, 0.0, mean, inv_std, state0, returns, traj, final_state,
-                        moments, status, kNoSide);
-        return launch_status();
-    }
-    if (use_quad3(p, n_roll, H, traj != nullptr)) {
-        const unsigned grid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-        SW_DISPATCH_QUAD(false, traj != nullptr, moments != nullptr,
-                         (hipStream_t)stream, C, n_roll, H, policies, (const double *)nullptr,
-                         (int64_t)0, 0.0, mean, inv_std, state0, returns, traj, final_state,
-                         moments, status, kNoSide);
-        return launch_status();
-    }
-    if (use_row(p, n_roll, H, traj != nullptr)) {
-        const unsigned grid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-        SW_DISPATCH_ROW(p->n, false, traj != nullptr, moments != nullptr, (hipStream_t)stream, C,
-                        n_roll, H, policies, (const double *)nullptr, (int64_t)0, 0.0, mean,
-                        inv_std, state0, returns, traj, final_state, moments, status, kNoSide);
-        return launch_status();
-    }
-    const unsigned grid = (unsigned)((n_roll + kRollBlock - 1) / kRollBlock);
-    const sw::TwinConsts T = make_twin_consts(p);
-    if (is_twin(p)) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((rollout_kernel<NN, false, true>), dim3(grid),
-                                               dim3(kRollBlock), 0, (hipStream_t)stream, C, T, n_roll, H,
-                                               policies, (const double *)nullptr, (int64_t)0, 0.0, mean,
-                                               inv_std, state0, returns, traj, final_state, moments,
-                                               status));
-    } else {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((rollout_kernel<NN, false, false>), dim3(grid),
-                                               dim3(kRollBlock), 0, (hipStream_t)stream, C, T, n_roll, H,
-                                               policies, (const double *)nullptr, (int64_t)0, 0.0, mean,
-                                               inv_std, state0, returns, traj, final_state, moments,
-                                               status));
-    }
-    return launch_status();
+    const RolloutArgs a{policies, /*deltas=*/nullptr, /*dir_begin=*/0, /*nu=*/0.0, mean, inv_std, state0,
+                        returns,  traj, final_state, moments, status};
+    return launch_rollouts(p, plan_rollouts(p, n_roll, H, traj != nullptr), false, n_roll, H, a,
+                           (hipStream_t)stream);
 }
 
 int sw_safe_rollouts_f64(const sw_params *real, const sw_params *sim, int64_t n_roll, int32_t H,
@@ -2281,113 +2261,38 @@ int sw_safe_rollouts_f64(const sw_params *real, const sw_params *sim, int64_t n_
     if (n_roll == 0) return SW_OK;
     if (!policies || !returns) return SW_ERR_NULL;
     const sw::Consts Cr = make_consts(real), Cs = make_consts(sim);
-    if (use_oct3(real, n_roll, H, traj != nullptr)) {
+    const RolloutPlan plan = plan_rollouts(real, n_roll, H, traj != nullptr, /*allow_quad=*/false);
+    const dim3 grid(plan.rollout_blocks), block(plan.block);
+    const hipStream_t st = (hipStream_t)stream;
+    bool known_n = true;
+    switch (plan.form) {
+    case Form::Oct3: {
         // n = 3, up to 8192 rollouts: the mirror-quad form (one geometry, two dynamics per env-step)
-        const unsigned ogrid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
         const double tq_ratio = Cs.c12 / Cr.c12;
-#define SW_LAUNCH_SAFE_OCT(TRAJ, VIOL)                                                                          \
-    hipLaunchKernelGGL((safe_rollout_oct3_kernel<TRAJ, VIOL>), dim3(ogrid), dim3(kOctBlock), 0,                 \
-                       (hipStream_t)stream, Cr, Cs, tq_ratio, n_roll, H, policies, cost_kind, cost_index,       \
-                       sim_thresh, real_thresh, returns, traj, first_refused, violations, status)
-        if (traj) {
-            if (violations) SW_LAUNCH_SAFE_OCT(true, true); else SW_LAUNCH_SAFE_OCT(true, false);
-        } else {
-            if (violations) SW_LAUNCH_SAFE_OCT(false, true); else SW_LAUNCH_SAFE_OCT(false, false);
-        }
-#undef SW_LAUNCH_SAFE_OCT
-        return launch_status();
+        with_bools([&](auto TRAJ, auto VIOL) {
+            hipLaunchKernelGGL((safe_rollout_oct3_kernel<TRAJ.value, VIOL.value>), grid, block, 0, st, Cr, Cs,
+                               tq_ratio, n_roll, H, policies, cost_kind, cost_index, sim_thresh, real_thresh,
+                               returns, traj, first_refused, violations, status);
+        }, traj != nullptr, violations != nullptr);
+        break;
     }
-    if (use_row(real, n_roll, H, traj != nullptr)) {
+    case Form::Row:
         // n = 4..8 while SIMDs are idle: the row form (two row_steps per env-step)
-        const unsigned rgrid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-#define SW_LAUNCH_SAFE_ROW(NN_)                                                                                 \
-    hipLaunchKernelGGL((safe_rollout_row_kernel<NN_>), dim3(rgrid), dim3(kRowBlock), 0, (hipStream_t)stream, Cr, \
-                       Cs, n_roll, H, policies, cost_kind, cost_index, sim_thresh, real_thresh,                 \
-                       violations ? 1 : 0, returns, traj, traj ? 1 : 0, first_refused, violations, status)
-        switch (real->n) {
-        case 4: SW_LAUNCH_SAFE_ROW(4); break;
-        case 5: SW_LAUNCH_SAFE_ROW(5); break;
-        case 6: SW_LAUNCH_SAFE_ROW(6); break;
-        case 7: SW_LAUNCH_SAFE_ROW(7); break;
-        default: SW_LAUNCH_SAFE_ROW(8); break;
-        }
-#undef SW_LAUNCH_SAFE_ROW
-        return launch_status();
+        known_n = with_n<4, 8>(real->n, [&](auto N) {
+            hipLaunchKernelGGL((safe_rollout_row_kernel<N.value>), grid, block, 0, st, Cr, Cs, n_roll, H, policies,
+                               cost_kind, cost_index, sim_thresh, real_thresh, violations ? 1 : 0, returns, traj,
+                               traj ? 1 : 0, first_refused, violations, status);
+        });
+        break;
+    default:   // the lane form (there is no safe quad kernel: allow_quad above)
+        known_n = with_n<2, 8>(real->n, [&](auto N) {
+            hipLaunchKernelGGL((safe_rollout_kernel<N.value>), grid, block, 0, st, Cr, Cs, n_roll, H, policies,
+                               cost_kind, cost_index, sim_thresh, real_thresh, returns, traj, first_refused,
+                               violations, status);
+        });
+        break;
     }
-    const unsigned grid = (unsigned)((n_roll + kRollBlock - 1) / kRollBlock);
-    SW_DISPATCH_N(real->n, hipLaunchKernelGGL((safe_rollout_kernel<NN>), dim3(grid), dim3(kRollBlock), 0,
-                                              (hipStream_t)stream, Cr, Cs, n_roll, H, policies, cost_kind,
-                                              cost_index, sim_thresh, real_thresh, returns, traj, first_refused,
-                                              violations, status));
-    return launch_status();
-}
-
-// side: what the launch carries besides the rollouts (pipeline only); *side_taken tells whether
-// the chosen kernel could take it (the segment-per-lane kernels can, the lane kernel cannot).
-static int launch_ars_rollouts(const sw_params *p, int64_t dir_begin, int64_t n_dir, int32_t H,
-                               const double *policy, const double *deltas, double nu,
-                               const double *mean, const double *inv_std, double *returns,
-                               double *traj, double *moments, int32_t *status, void *stream,
-                               const SideJob *side, bool *side_taken)
-{
-    int rc = validate_params(p);   // the public entry points have cleared stale errors already
-    if (rc) return rc;
-    if (n_dir < 0 || H < 0 || dir_begin < 0) return SW_ERR_SIZE;
-    if (side_taken) *side_taken = false;
-    if (n_dir == 0) return SW_OK;
-    if (!policy || !deltas || !returns) return SW_ERR_NULL;
-    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
-    const sw::Consts C = make_consts(p);
-    const int64_t n_roll = 2 * n_dir;
-    if (use_oct3(p, n_roll, H, traj != nullptr)) {
-        unsigned grid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-        SideJob sj = side ? *side : kNoSide;
-        grid += side_attach_cov(sj, grid, kOctBlock, 2 * p->n + 2);
-        if (side_taken) *side_taken = side != nullptr;
-        SW_DISPATCH_OCT(true, traj != nullptr, moments != nullptr,
-                        (hipStream_t)stream, C, n_roll, H, policy, deltas, dir_begin, nu, mean,
-                        inv_std, (const double *)nullptr, returns, traj, (double *)nullptr,
-                        moments, status, sj);
-        return launch_status();
-    }
-    if (use_quad3(p, n_roll, H, traj != nullptr)) {
-        unsigned grid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-        SideJob sj = side ? *side : kNoSide;
-        grid += side_attach_cov(sj, grid, kRollBlock, 2 * p->n + 2);
-        if (side_taken) *side_taken = side != nullptr;
-        SW_DISPATCH_QUAD(true, traj != nullptr, moments != nullptr,
-                         (hipStream_t)stream, C, n_roll, H, policy, deltas, dir_begin, nu, mean,
-                         inv_std, (const double *)nullptr, returns, traj, (double *)nullptr,
-                         moments, status, sj);
-        return launch_status();
-    }
-    if (use_row(p, n_roll, H, traj != nullptr)) {
-        unsigned grid = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-        SideJob sj = side ? *side : kNoSide;
-        grid += side_attach_cov(sj, grid, kRowBlock, 2 * p->n + 2);
-        if (side_taken) *side_taken = side != nullptr;
-        SW_DISPATCH_ROW(p->n, true, traj != nullptr, moments != nullptr, (hipStream_t)stream, C,
-                        n_roll, H, policy, deltas, dir_begin, nu, mean, inv_std,
-                        (const double *)nullptr, returns, traj, (double *)nullptr, moments, status,
-                        sj);
-        return launch_status();
-    }
-    const unsigned grid = (unsigned)((n_roll + kRollBlock - 1) / kRollBlock);
-    const sw::TwinConsts T = make_twin_consts(p);
-    if (is_twin(p)) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((rollout_kernel<NN, true, true>), dim3(grid),
-                                               dim3(kRollBlock), 0, (hipStream_t)stream, C, T, n_roll, H,
-                                               policy, deltas, dir_begin, nu, mean, inv_std,
-                                               (const double *)nullptr, returns, traj, (double *)nullptr,
-                                               moments, status));
-    } else {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((rollout_kernel<NN, true, false>), dim3(grid),
-                                               dim3(kRollBlock), 0, (hipStream_t)stream, C, T, n_roll, H,
-                                               policy, deltas, dir_begin, nu, mean, inv_std,
-                                               (const double *)nullptr, returns, traj, (double *)nullptr,
-                                               moments, status));
-    }
-    return launch_status();
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 int sw_ars_rollouts_f64(const sw_params *p, int64_t dir_begin, int64_t n_dir, int32_t H,
@@ -2395,19 +2300,24 @@ int sw_ars_rollouts_f64(const sw_params *p, int64_t dir_begin, int64_t n_dir, in
                         const double *inv_std, double *returns, double *traj, double *moments,
                         int32_t *status, void *stream)
 {
-    (void)hipGetLastError();   // public entry point: drop a stale error once (see check_params)
-    return launch_ars_rollouts(p, dir_begin, n_dir, H, policy, deltas, nu, mean, inv_std, returns,
-                               traj, moments, status, stream, nullptr, nullptr);
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_dir < 0 || H < 0 || dir_begin < 0) return SW_ERR_SIZE;
+    if (n_dir == 0) return SW_OK;
+    if (!deltas) return SW_ERR_NULL;
+    const RolloutArgs a{policy,  deltas, dir_begin, nu, mean, inv_std, /*state0=*/nullptr,
+                        returns, traj, /*final_state=*/nullptr, moments, status};
+    return launch_rollouts(p, plan_rollouts(p, 2 * n_dir, H, traj != nullptr), true, 2 * n_dir, H, a,
+                           (hipStream_t)stream);
 }
 
-// The ARS simulator gate (ars_agent.py:144-157): the 2 n_dir simulator rollouts of launch_ars_rollouts in
+// The ARS simulator gate (ars_agent.py:144-157): the 2 n_dir simulator rollouts of sw_ars_rollouts_f64 in
 // the form it would pick without trajectories, returns only, the decision fused into the epilogue.
 int sw_ars_gate_f64(const sw_params *sim, int64_t dir_begin, int64_t n_dir, int32_t H, const double *policy,
                     const double *deltas, double nu, const double *mean, const double *inv_std,
                     double sim_thresh, int32_t *admit, double *returns, int32_t *status, void *stream)
 {
-    (void)hipGetLastError();   // public entry point: drop a stale error once (see check_params)
-    int rc = validate_params(sim);
+    int rc = check_params(sim);
     if (rc) return rc;
     if (n_dir < 0 || H < 0 || dir_begin < 0) return SW_ERR_SIZE;
     if (n_dir == 0) return SW_OK;
@@ -2416,42 +2326,29 @@ int sw_ars_gate_f64(const sw_params *sim, int64_t dir_begin, int64_t n_dir, int3
     const sw::Consts C = make_consts(sim);
     const int64_t n_roll = 2 * n_dir;
     const hipStream_t st = (hipStream_t)stream;
-    const unsigned rows = (unsigned)((n_roll + kMomGroup - 1) / kMomGroup);
-    if (use_oct3(sim, n_roll, H, false)) {
-        hipLaunchKernelGGL(ars_gate_oct3_kernel, dim3(rows), dim3(kOctBlock), 0, st, C, n_roll, H, policy, deltas,
-                           dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status, kNoSide);
-        return launch_status();
-    }
-    if (use_quad3(sim, n_roll, H, false)) {
-        hipLaunchKernelGGL(ars_gate_quad3_kernel, dim3(rows), dim3(kRollBlock), 0, st, C, n_roll, H, policy, deltas,
-                           dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status, kNoSide);
-        return launch_status();
-    }
-    if (use_row(sim, n_roll, H, false)) {
-        switch (sim->n) {
-#define SW_GATE_ROW(NN)                                                                                           \
-    case NN:                                                                                                      \
-        hipLaunchKernelGGL(ars_gate_row_kernel<NN>, dim3(rows), dim3(kRowBlock), 0, st, C, n_roll, H, policy,    \
-                           deltas, dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status, kNoSide);    \
+    const RolloutPlan plan = plan_rollouts(sim, n_roll, H, false);
+    const dim3 grid(plan.rollout_blocks), block(plan.block);
+    auto segment_per_lane = [&](auto *kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, C, n_roll, H, policy, deltas, dir_begin, nu, mean, inv_std,
+                           sim_thresh, admit, returns, status, kNoSide);
+    };
+    bool known_n = true;
+    switch (plan.form) {
+    case Form::Oct3: segment_per_lane(ars_gate_oct3_kernel); break;
+    case Form::Quad3: segment_per_lane(ars_gate_quad3_kernel); break;
+    case Form::Row:
+        known_n = with_n<4, 8>(sim->n, [&](auto N) { segment_per_lane(ars_gate_row_kernel<N.value>); });
         break;
-        SW_GATE_ROW(4) SW_GATE_ROW(5) SW_GATE_ROW(6) SW_GATE_ROW(7) SW_GATE_ROW(8)
-#undef SW_GATE_ROW
-        default: return SW_ERR_SEGMENTS;
-        }
-        return launch_status();
+    case Form::Lane: {
+        const sw::TwinConsts T = make_twin_consts(sim);
+        known_n = with_n<2, 8>(sim->n, [&](auto N, auto TWIN) {
+            hipLaunchKernelGGL((ars_gate_kernel<N.value, TWIN.value>), grid, block, 0, st, C, T, n_roll, H, policy,
+                               deltas, dir_begin, nu, mean, inv_std, sim_thresh, admit, returns, status);
+        }, is_twin(sim));
+        break;
     }
-    const unsigned grid = (unsigned)((n_roll + kRollBlock - 1) / kRollBlock);
-    const sw::TwinConsts T = make_twin_consts(sim);
-    if (is_twin(sim)) {
-        SW_DISPATCH_N(sim->n, hipLaunchKernelGGL((ars_gate_kernel<NN, true>), dim3(grid), dim3(kRollBlock), 0, st, C,
-                                                 T, n_roll, H, policy, deltas, dir_begin, nu, mean, inv_std,
-                                                 sim_thresh, admit, returns, status));
-    } else {
-        SW_DISPATCH_N(sim->n, hipLaunchKernelGGL((ars_gate_kernel<NN, false>), dim3(grid), dim3(kRollBlock), 0, st, C,
-                                                 T, n_roll, H, policy, deltas, dir_begin, nu, mean, inv_std,
-                                                 sim_thresh, admit, returns, status));
     }
-    return launch_status();
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 static int launch_update(const sw_params *p, int64_t n_dir, const GatherView &gv,
@@ -2464,14 +2361,12 @@ static int launch_update(const sw_params *p, int64_t n_dir, const GatherView &gv
     // the moment rows) sets it.  256 threads per workgroup up to 1024 directions, 1024 beyond: 2048
     // directions 11.6 -> ~6 us (rocprofv3).  The summation order is a function of n_dir only, so every
     // rank of a sharded run and the single-process run of the same problem still get the same bits.
-    if (n_dir >= kUpdWideFrom)
-        hipLaunchKernelGGL(ars_update_kernel<kUpdBlockWide>, dim3(md + 1), dim3(kUpdBlockWide), 0,
-                           (hipStream_t)stream, d, md, (int32_t)n_dir, gv, deltas, policy, alpha, b, top_b,
-                           running, (double)n_new_states, mean, inv_std, sigma_out);
-    else
-        hipLaunchKernelGGL(ars_update_kernel<kUpdBlock>, dim3(md + 1), dim3(kUpdBlock), 0, (hipStream_t)stream,
-                           d, md, (int32_t)n_dir, gv, deltas, policy, alpha, b, top_b, running,
-                           (double)n_new_states, mean, inv_std, sigma_out);
+    with_bools([&](auto WIDE) {
+        constexpr int kBlock = WIDE.value ? kUpdBlockWide : kUpdBlock;
+        hipLaunchKernelGGL(ars_update_kernel<kBlock>, dim3(md + 1), dim3(kBlock), 0, (hipStream_t)stream, d, md,
+                           (int32_t)n_dir, gv, deltas, policy, alpha, b, top_b, running, (double)n_new_states,
+                           mean, inv_std, sigma_out);
+    }, n_dir >= kUpdWideFrom);
     return launch_status();
 }
 
@@ -2515,8 +2410,8 @@ int sw_ars_update_gathered_f64(const sw_params *p, int64_t n_dir, const double *
                          mean, inv_std, sigma_out, stream);
 }
 
-// One covariance pass with workgroups of `block` (64 or 256) threads.  The pipeline runs the pass
-// it still owes with the block size of the rollout kernel that would have carried it, so a flushed
+// One covariance pass with workgroups of `block` (64, 128 or 256) threads.  The pipeline runs the pass
+// it still owes with owed_cov_block() of the rollout launch that left it, so a flushed
 // pass sums in exactly the order the ride-along pass would have (bit-identical resume).
 static int launch_traj_moments(const sw_params *p, int64_t n_roll, int32_t H, const double *traj,
                                double *acc, int block, bool riding, void *stream)
@@ -2525,21 +2420,20 @@ static int launch_traj_moments(const sw_params *p, int64_t n_roll, int32_t H, co
     if (n_roll == 0 || H == 0) return SW_OK;
     if (!traj || !acc) return SW_ERR_NULL;
     const CovTiling t = cov_tiling(n_roll, H, block, 2 * p->n + 2, riding);
-    const dim3 grid(t.nbx * t.ny);
-    if (block == kRollBlock) {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((traj_moments_kernel<2 * NN + 2, kRollBlock>), grid,
-                                               dim3(kRollBlock), 0, (hipStream_t)stream, n_roll, H,
-                                               traj, acc, t.nbx, t.tchunk));
-    } else if (block == kOctBlock) {   // owed by a mirror-quad launch (n = 3 only)
+    auto launch = [&](auto *kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(t.nbx * t.ny), dim3(threads), 0, (hipStream_t)stream, n_roll, H, traj, acc,
+                           t.nbx, t.tchunk);
+    };
+    if (block == kOctBlock) {   // owed by a mirror-quad launch (n = 3 only)
         if (p->n != 3) return SW_ERR_SIZE;
-        hipLaunchKernelGGL((traj_moments_kernel<8, kOctBlock>), grid, dim3(kOctBlock), 0,
-                           (hipStream_t)stream, n_roll, H, traj, acc, t.nbx, t.tchunk);
-    } else {
-        SW_DISPATCH_N(p->n, hipLaunchKernelGGL((traj_moments_kernel<2 * NN + 2, kMomBlock>), grid,
-                                               dim3(kMomBlock), 0, (hipStream_t)stream, n_roll, H,
-                                               traj, acc, t.nbx, t.tchunk));
+        launch(traj_moments_kernel<8, kOctBlock>, kOctBlock);
+        return launch_status();
     }
-    return launch_status();
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto ONE_WAVE) {
+        constexpr int kBlock = ONE_WAVE.value ? kRollBlock : kMomBlock;
+        launch(traj_moments_kernel<2 * N.value + 2, kBlock>, kBlock);
+    }, block == kRollBlock);
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
 int64_t sw_cov_acc_doubles(const sw_params *p, int64_t n_roll, int32_t H)
@@ -2548,9 +2442,11 @@ int64_t sw_cov_acc_doubles(const sw_params *p, int64_t n_roll, int32_t H)
     const int d = 2 * p->n + 2;
     int64_t tiles = 0;
     if (n_roll > 0 && H > 0) {
+        // every pass the batch can be given: riding or standalone, owed by a launch of any form
+        // (sw_traj_moments_f64's standalone pass has the lane form's block)
         for (int riding = 0; riding < 2; ++riding)
-            for (int block : {kRollBlock, kOctBlock, kMomBlock}) {
-                const CovTiling t = cov_tiling(n_roll, H, block, d, riding != 0);
+            for (Form f : kForms) {
+                const CovTiling t = cov_tiling(n_roll, H, owed_cov_block(f), d, riding != 0);
                 const int64_t n = (int64_t)t.nbx * t.ny;
                 tiles = n > tiles ? n : tiles;
             }
@@ -2626,16 +2522,11 @@ static int env1_run(sw_env1 *e, const sw_params *p, bool accel, int32_t *status)
     int caller_device = e->device;
     if (hipGetDevice(&caller_device) != hipSuccess) return SW_ERR_LAUNCH;
     if (caller_device != e->device && hipSetDevice(e->device) != hipSuccess) return SW_ERR_LAUNCH;
-#define SW_ENV1_LAUNCH(TW, AC)                                                                     \
-    SW_DISPATCH_N(p->n, hipLaunchKernelGGL((env1_kernel<NN, TW, AC>), dim3(1), dim3(kWave), 0,     \
-                                           e->stream, C, T, e->io_dev, st_dev, flag_dev, seq))
-    if (is_twin(p)) {
-        if (accel) { SW_ENV1_LAUNCH(true, true); } else { SW_ENV1_LAUNCH(true, false); }
-    } else {
-        if (accel) { SW_ENV1_LAUNCH(false, true); } else { SW_ENV1_LAUNCH(false, false); }
-    }
-#undef SW_ENV1_LAUNCH
-    rc = launch_status();
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN, auto ACCEL) {
+        hipLaunchKernelGGL((env1_kernel<N.value, TWIN.value, ACCEL.value>), dim3(1), dim3(kWave), 0, e->stream, C, T,
+                           e->io_dev, st_dev, flag_dev, seq);
+    }, is_twin(p), accel);
+    rc = known_n ? launch_status() : SW_ERR_SEGMENTS;
     if (caller_device != e->device) (void)hipSetDevice(caller_device);
     if (rc) return rc;
     for (int64_t spins = 0; *flag_host != seq; ++spins) {
@@ -2897,16 +2788,15 @@ int sw_ars_iteration_rollouts_f64(sw_ars_pipeline *pl, int slot, const sw_params
             hipEventRecord(ev.first, main) != hipSuccess)
             return SW_ERR_LAUNCH;
     }
-    const bool oct = use_oct3(p, 2 * n_dir, H, traj != nullptr);
-    const bool quad = use_quad3(p, 2 * n_dir, H, traj != nullptr);   // (true for oct launches too)
-    const bool row = !quad && use_row(p, 2 * n_dir, H, traj != nullptr);
-    const int block = oct ? kOctBlock : (quad ? kRollBlock : kMomBlock);   // kRowBlock == kMomBlock
+    // ONE plan for the ride-along decision below and for the launch itself
+    const RolloutPlan plan = plan_rollouts(p, 2 * n_dir, H, traj != nullptr);
+    const int cov_block = owed_cov_block(plan.form);
     SideJob sj = kNoSide;
     sj.flag = pl->flag_dev;
     sj.flag_value = k;
     // the owed pass rides along when this launch's kernel can carry it in the tiling it is owed in
-    const bool ride = pl->cov_traj && (quad || row) && pl->cov_params.n == p->n &&
-                      pl->cov_block == block;
+    const bool ride = pl->cov_traj && plan.carries_side && pl->cov_params.n == p->n &&
+                      pl->cov_block == cov_block;
     if (pl->cov_traj && !ride) {
         rc = flush_owed_cov(pl, main);
         if (rc) return rc;
@@ -2917,16 +2807,15 @@ int sw_ars_iteration_rollouts_f64(sw_ars_pipeline *pl, int slot, const sw_params
         sj.cov_rolls = pl->cov_rolls;
         sj.cov_H = pl->cov_H;
     }
-    bool taken = false;
-    if (!quad && !row) {
+    if (!plan.carries_side) {
         // the lane kernel takes no side job: the flag as a launch of its own in front of it
         hipLaunchKernelGGL(flag_kernel, dim3(1), dim3(1), 0, main, pl->flag_dev, k);
         rc = launch_status();   // a failed flag launch must surface here, not iterations later in wait_flag
         if (rc) return rc;
-        sj = kNoSide;
     }
-    rc = launch_ars_rollouts(p, dir_begin, n_dir, H, policy, deltas_dev, nu, mean, inv_std,
-                             returns, traj, moments, status, stream, &sj, &taken);
+    const RolloutArgs a{policy,  deltas_dev, dir_begin, nu, mean, inv_std, /*state0=*/nullptr,
+                        returns, traj, /*final_state=*/nullptr, moments, status};
+    rc = launch_rollouts(p, plan, true, 2 * n_dir, H, a, main, &sj);
     if (timed_launch) {
         (void)hipEventRecord(ev.second, main);
         pl->timed.push_back(ev);
@@ -2940,7 +2829,7 @@ int sw_ars_iteration_rollouts_f64(sw_ars_pipeline *pl, int slot, const sw_params
         pl->cov_acc = cov_acc;
         pl->cov_rolls = 2 * n_dir;
         pl->cov_H = H;
-        pl->cov_block = block;
+        pl->cov_block = cov_block;
         pl->cov_params = *p;
     }
     return SW_OK;
