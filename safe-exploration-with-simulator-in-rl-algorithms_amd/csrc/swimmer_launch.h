@@ -1,0 +1,371 @@
+// swimmer_launch.h -- what the kernel families of libswimmer_hip.so share (internal; the C ABI is
+// include/swimmer_hip.h): constants, tuning knobs, argument checks, the run-time-to-template dispatch, the rollout
+// plan, and the declarations of the launch functions that cross the files.
+//
+// All arithmetic is fp64 on the vector ALUs; there is no MFMA (the largest contraction on this
+// path is 8x8) and no LDS in the hot loops (neighbour data moves by DPP).  One source file per kernel family, each
+// with its kernels, their private device helpers and the host function that launches them (swimmer_kernels.hip
+// includes the families' files into the one translation unit their code depends on; its header says why):
+//
+//   swimmer_step.hip
+//   step_kernel<N,TWIN,NT>     one physics step, SoA in / SoA out, one env per lane; HBM-bound
+//                              at large n_env (algorithmic traffic 16 (2n+2) + 8 (n-1) + 8 bytes
+//                              per env-step); NT = nontemporal accesses for streaming batches.
+//                              A two-envs-per-lane variant with 16-byte accesses measured SLOWER
+//                              (4.87 vs 5.62 TB/s: 90 VGPRs, fewer loads in flight) and was dropped.
+//   accel_kernel<N,TWIN>       accelerations only
+//   step_residual*_kernel      the estimator's objective, one parameter set or a population
+//   env1_kernel                one swimmer handed over in host memory (sw_env1)
+//   swimmer_rollout_n3.hip
+//   rollout_oct3_kernel        n = 3, H steps in one launch, one segment per lane WITH LANE ROLES: two
+//                              mirror quads per rollout (sine / cosine, Gdot_x / Gdot_y;
+//                              swimmer_oct3.h): the latency form, instruction-issue bound; up to
+//                              8192 rollouts (one wave per SIMD)
+//   rollout_quad3_kernel       n = 3, one DPP quad per rollout (swimmer_quad3.h): 8193 .. 16384 rollouts
+//   swimmer_rollout_row.hip
+//   rollout_row_kernel<N>      n = 4..8, one segment per lane, one rollout per 16-lane DPP row
+//                              (swimmer_row.h)
+//   swimmer_rollout_lane.hip
+//   rollout_kernel<N,ARS,TWIN> any n, ONE ROLLOUT PER LANE: the throughput form for batches that
+//                              fill the chip, and the only form of the twin model
+//   (each rollout file also holds its form's ARS gate and safe-exploration kernels)
+//   swimmer_update.hip
+//   ars_update_kernel          sigma_R, policy step, V2 statistics merge; pure latency between
+//                              two rollout launches: one round of loads, then LDS only
+//   swimmer_cov.hip, swimmer_cov.h
+//   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound; its tile code
+//                              (swimmer_cov.h) also rides along in the segment-per-lane rollout launches (SideJob)
+//   swimmer_abi.hip
+//   the rollout entry points and the native ARS iteration pipeline (sw_ars_pipeline_*: copy stream, progress
+//   flag, 4-slot buffer ring; the covariance pass rides along in the next rollout launch)
+// Which of the four rollout forms a launch takes, and with which grid, is decided in ONE place,
+// plan_rollouts() (swimmer_abi.hip); run-time flags and n become template arguments through with_bools() /
+// with_n<LO, HI>(), next to the kernels they name.
+//
+// Kernels and the types they take stay in unnamed namespaces (their mangled names are what the ISA tools, the
+// placement test and the profiles key on), so nothing of such a type can cross a file: what does cross is in
+// namespace sw_launch below, with hidden visibility -- the library's dynamic symbols are the C ABI only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <climits>
+#include <cstdlib>
+#include <type_traits>
+#include <utility>
+
+#include "../../include/swimmer_hip.h"
+#include "swimmer_device.h"
+#include "swimmer_twin.h"
+
+// Where a rollout kernel's hot loop starts inside a 64-byte line of code.  A lone wave's issue rate depends on
+// it: the same instructions, byte for byte, ran 0.2267 and 0.2346 ms per launch (n = 3) after an unrelated
+// change elsewhere in the file had moved the loop by 16 bytes, and the one-step loops of the row kernel lose
+// 4-11 % when their head is not 8-byte aligned (profiles/r03_p_ab_n3.log, r03_p_loop_pad_sweep_*.log).
+// SW_PIN_LOOP aligns the code that follows to a line and puts PAD s_nops (4 bytes each) behind the boundary;
+// the pads below are the best of a sweep over 0..7 on the GPU (scripts/ab_probe.sh over builds with
+// -DSW_OCT_LOOP_PAD=k -DSW_QUAD_LOOP_PAD=k -DSW_ROW_LOOP_PAD=k).  Sweep again after changing what lies
+// between a pin and its loop.
+#define SW_PIN_LOOP(PAD) asm volatile(".p2align 6\n\t.fill %0, 4, 0xbf800000" ::"n"(PAD))
+#ifndef SW_OCT_UNROLL
+#define SW_OCT_UNROLL 8   // steps per trip of the mirror-quad kernel's main loop (4 or 8)
+#endif
+// mirror-quad kernel, by what the loop carries (trajectory capture, V2 moment sums): every instantiation is
+// its own code, with its own best offset (profiles/r03_x_inst_sweep.log); -DSW_OCT_LOOP_PAD=k overrides all four
+#ifdef SW_OCT_LOOP_PAD
+constexpr int oct_loop_pad(bool, bool) { return SW_OCT_LOOP_PAD; }
+#else
+constexpr int oct_loop_pad(bool traj, bool mom) { return traj ? (mom ? 5 : 6) : (mom ? 6 : 2); }
+#endif
+#ifndef SW_QUAD_LOOP_PAD
+#define SW_QUAD_LOOP_PAD 0
+#endif
+// row kernel, n = 4..8; swept with capture + moments for every n, and for the other three forms at n = 6;
+// -DSW_ROW_LOOP_PAD=k overrides all of them for a sweep
+#ifdef SW_ROW_LOOP_PAD
+constexpr int row_loop_pad(int, bool, bool) { return SW_ROW_LOOP_PAD; }
+#else
+constexpr int row_loop_pad(int n, bool traj, bool mom)
+{
+    if (n == 6 && !(traj && mom)) return traj ? 6 : 4;
+    return n == 4 ? 5 : n == 5 ? 0 : n == 6 ? 5 : n == 7 ? 6 : 1;
+}
+#endif
+
+// steps per trip of the quad kernel's loop (measurement knob; 2 measured +5 ns per step)
+#ifndef SW_QUAD_UNROLL
+#define SW_QUAD_UNROLL 4
+#endif
+// Cache policy of the trajectory stores of the segment-per-lane kernels (gfx940+ encoding:
+// 1 = sc0, 2 = nt, 16 = sc1).  sc1 = device-scope write-through: the 65 MB a launch stores do not
+// pile up as dirty lines in the XCDs' L2s, so the write-back at the end of the kernel -- which sits
+// on the critical path rollout -> update -- is short.  Same-box A/B (profiles/r02_d_ab_store_policy.log):
+// plain 0.2564 ms per launch / 0.2675 ms per iteration, nt 0.2550 / 0.2658, sc0 0.2566 / 0.2673,
+// sc1 0.2520 / 0.2628 (sc0 + sc1 and sc1 + nt the same as sc1).  (The lane kernel's stores in the
+// saturated regime gain nothing from nontemporal stores: 4.58 vs 4.55 TB/s, scripts/saturated_probe.py.)
+#ifndef SW_TRAJ_STORE_AUX
+#define SW_TRAJ_STORE_AUX 16
+#endif
+// n = 3 rollouts: the mirror-quad kernel (swimmer_oct3.h) by default, or the quad kernel
+#ifndef SW_N3_DEFAULT_OCT
+#define SW_N3_DEFAULT_OCT true
+#endif
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kStepBlock = 256;
+constexpr int kRollBlock = 64;   // one wave per workgroup: every wave gets a SIMD to itself
+constexpr int kOctBlock = 128;   // mirror-quad kernel: 8 rollouts per wave, 16 (= one V2 moment row) per workgroup
+constexpr int kMomGroup = 16;    // rollouts per V2 moment row (same partition in every kernel)
+constexpr int64_t kQuadMaxRollouts = 16384;  // above this every SIMD already has a wave
+constexpr int64_t kRowMaxRollouts = 8192;    // row kernel (n >= 4): 4 rollouts per wave
+constexpr int kRowBlock = 256;               // 16 rollouts = one V2 moment row per workgroup
+constexpr int kUpdBlock = 256;        // update kernel: threads per workgroup up to kUpdWideFrom directions ...
+constexpr int kUpdBlockWide = 1024;   // ... and beyond (a thread's share of the directions stays short)
+constexpr int32_t kUpdWideFrom = 1025;
+constexpr int kMomBlock = 256;        // standalone covariance pass: threads per workgroup
+constexpr int64_t kStepStreamBytes = (int64_t)256 << 20;   // beyond the Infinity Cache: nontemporal accesses
+constexpr int kPopGroup = 8;          // sw_step_residual_pop_f64: candidates per workgroup, ...
+constexpr int64_t kPopMaxCandidates = (int64_t)65535 * kPopGroup;   // ... and at most 65535 groups (grid.y)
+constexpr double kHalfPi = 1.57079632679489661923;  // math.pi / 2 (remy_swimmer_env.py:65)
+constexpr double kTwinStart = 0.001;                // SwimmerEnvironment.cpp:41
+
+sw::Consts make_consts(const sw_params *p)
+{
+    return sw::consts_of(p->n, p->l_i, p->m_i, p->k, p->h, p->dir_x, p->dir_y);
+}
+
+sw::TwinConsts make_twin_consts(const sw_params *p)
+{
+    return sw::TwinConsts{p->l_i, p->m_i, p->k, p->h, p->dir_x, p->dir_y};
+}
+
+inline bool is_twin(const sw_params *p) { return (p->flags & SW_FLAG_MODEL_TWIN) != 0; }
+
+// Argument check shared by the entry points and the internal launchers (touches no HIP state).
+int validate_params(const sw_params *p)
+{
+    if (!p) return SW_ERR_NULL;
+    if (p->n < 2 || p->n > SW_MAX_SEGMENTS) return SW_ERR_SEGMENTS;
+    if (p->flags & ~(SW_FLAG_ROLLOUT_LANE | SW_FLAG_ROLLOUT_QUAD | SW_FLAG_MODEL_TWIN)) return SW_ERR_PARAM;
+    if (!(p->l_i > 0.0) || !(p->m_i > 0.0) || !isfinite(p->l_i) || !isfinite(p->m_i) ||
+        !isfinite(p->k) || !isfinite(p->h) || !isfinite(p->dir_x) || !isfinite(p->dir_y))
+        return SW_ERR_PARAM;
+    return SW_OK;
+}
+
+// First call of every PUBLIC entry point: drops, once, whatever error an earlier HIP call of this
+// thread left behind (a failed call of the caller's, hipErrorNotReady from an event query, ...), so
+// that launch_status() reports OUR launches and does not blame a stale error on them.  Internal
+// launchers use validate_params(): clearing again in the middle of an entry point would discard
+// the error of a launch the entry point itself made a moment earlier.
+int check_params(const sw_params *p)
+{
+    (void)hipGetLastError();
+    return validate_params(p);
+}
+
+int launch_status()
+{
+    return hipGetLastError() == hipSuccess ? SW_OK : SW_ERR_LAUNCH;
+}
+
+// ---- dispatch on the segment count -------------------------------------------------
+// Run-time values to template arguments.  f is a generic lambda that takes them BY VALUE as
+// std::integral_constant, so `N.value` / `TRAJ.value` are constant expressions inside it.
+template <class F> void with_bools(F &&f) { f(); }
+template <class F, class... Rest> void with_bools(F &&f, bool b, Rest... rest)
+{
+    if (b)
+        with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else
+        with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
+// f(N, bools...) for n in the closed range LO..HI -- the only values a kernel is instantiated for;
+// false (the caller's SW_ERR_SEGMENTS) when n is outside it.
+template <int LO, int HI, class F, class... Bools> bool with_n(int n, F &&f, Bools... bools)
+{
+    if constexpr (LO > HI) {
+        return false;
+    } else {
+        if (n != LO) return with_n<LO + 1, HI>(n, f, bools...);
+        with_bools([&](auto... cs) { f(std::integral_constant<int, LO>{}, cs...); }, bools...);
+        return true;
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// The ARS simulator gate (sw_ars_gate_f64, ars_agent.py:146-157): direction i is admitted unless one of
+// its two simulator returns is <= the threshold.  `x <= thr` is false for a NaN on either side, so a
+// NaN return or a NaN threshold admits, as in the reference.  Rollouts 2i and 2i + 1 of a direction
+// sit in one wave in every kernel form, XOR lanes apart: one ds_swizzle (bit-mask mode, XOR < 32)
+// hands each owner lane its partner's return, the even rollout's owner stores the flag.  Every lane
+// of the pair's owners must be active (both rollouts of a direction are valid or neither is).
+template <int XOR>
+__device__ __forceinline__ double swizzle_xor_f64(double v)
+{
+    static_assert(XOR > 0 && XOR < 32, "ds_swizzle bit-mask mode reaches lanes within 32");
+    constexpr int kPattern = 0x1f | (XOR << 10);   // and_mask 0x1f, or_mask 0, xor_mask XOR
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_ds_swizzle(lo, kPattern);
+    hi = __builtin_amdgcn_ds_swizzle(hi, kPattern);
+    return __hiloint2double(hi, lo);
+}
+
+template <int XOR>
+__device__ __forceinline__ void gate_store(double ret, int code, bool owner, int64_t r, double thr,
+                                           double *__restrict__ returns, int32_t *__restrict__ status,
+                                           int32_t *__restrict__ admit)
+{
+    const double partner = swizzle_xor_f64<XOR>(ret);
+    if (owner) {
+        if (returns) returns[r] = ret;
+        if (status) status[r] = code;
+        if ((r & 1) == 0) admit[r >> 1] = (!(ret <= thr) && !(partner <= thr)) ? 1 : 0;
+    }
+}
+
+// This lane's pre-combined policy row V_i = c12 (W_{i-1} - W_i), W = (P +- nu delta) diag(inv_std)
+// (ars_agent.py:141-142, environment.py:32-34; u_{-1} = u_{n-1} = 0: free ends), and
+// nbias = -V_i . mean.  cols[j]: the observation column of entry j (the quad kernel keeps its
+// row in rotated order).  Branch-free on purpose: every lane loads both neighbouring rows with a
+// clamped row index and SELECTS afterwards, so all 4 D + 2 D loads are in flight together and the
+// launch pays one memory latency instead of ~40 serial ones (measured: the prologue was most of
+// the ~6 us fixed cost of a rollout launch).
+template <int D, int M, bool ARS>
+__device__ __forceinline__ void load_policy_row(const double *__restrict__ pl,
+                                                const double *__restrict__ dl, double sgn, double nu,
+                                                const double *__restrict__ mean,
+                                                const double *__restrict__ inv_std, double c12,
+                                                int seg, const int (&cols)[D], double (&V)[D],
+                                                double &nbias)
+{
+    const int a_up = (seg >= 1) ? seg - 1 : 0, a_dn = (seg <= M - 1) ? seg : M - 1;
+    double pu[D], pd[D], du[D], dd[D], is[D], mn[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        pu[j] = pl[a_up * D + cols[j]];
+        pd[j] = pl[a_dn * D + cols[j]];
+    }
+    if (ARS) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            du[j] = dl[a_up * D + cols[j]];
+            dd[j] = dl[a_dn * D + cols[j]];
+        }
+    }
+    if (inv_std) {   // uniform
+#pragma unroll
+        for (int j = 0; j < D; ++j) is[j] = inv_std[cols[j]];
+    }
+    if (mean) {      // uniform
+#pragma unroll
+        for (int j = 0; j < D; ++j) mn[j] = mean[cols[j]];
+    }
+    nbias = 0.0;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        double wu = pu[j], wd = pd[j];
+        if (ARS) {   // ars_agent.py:141-142
+            wu = __dadd_rn(wu, sgn * __dmul_rn(nu, du[j]));
+            wd = __dadd_rn(wd, sgn * __dmul_rn(nu, dd[j]));
+        }
+        if (inv_std) {   // environment.py:32-33
+            wu = __dmul_rn(wu, is[j]);
+            wd = __dmul_rn(wd, is[j]);
+        }
+        const double up = (seg >= 1) ? wu : 0.0;
+        const double dn = (seg <= M - 1) ? wd : 0.0;
+        V[j] = c12 * (up - dn);
+        if (mean) nbias = __builtin_fma(-V[j], mn[j], nbias);
+    }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------
+// What crosses the files: the plan of a rollout launch, and one launch function per kernel form.  (The attribute
+// holds for one block of the namespace: the files that define these functions repeat it.)
+namespace sw_launch __attribute__((visibility("hidden"))) {
+
+// The four forms of a rollout launch (above), chosen in one place: plan_rollouts(), swimmer_abi.hip.
+enum class Form { Oct3, Quad3, Row, Lane };
+constexpr Form kForms[] = {Form::Oct3, Form::Quad3, Form::Row, Form::Lane};
+
+constexpr int form_block(Form f)
+{
+    return f == Form::Oct3 ? kOctBlock : f == Form::Row ? kRowBlock : kRollBlock;
+}
+
+// Workgroup size of the covariance pass that a launch of form f leaves owed: the pass rides along in a
+// launch of the same form, or is flushed with that form's workgroups.  The lane kernel carries no side
+// job, so its pass is always the flushed one, with the standalone pass's kMomBlock.
+constexpr int owed_cov_block(Form f) { return f == Form::Lane ? kMomBlock : form_block(f); }
+
+struct RolloutPlan {
+    Form form;
+    int block;                 // threads per workgroup
+    unsigned rollout_blocks;   // workgroups that run rollouts (a side job's come behind them)
+    bool carries_side;         // the form's kernels take a SideJob
+};
+
+// What the rollout kernels take besides the model and the batch.  Plain rollouts (sw_rollout_f64): one
+// policy per rollout, no deltas.  ARS rollouts: one policy, +-nu deltas[dir_begin + i], no state0 /
+// final_state.
+struct RolloutArgs {
+    const double *policies, *deltas;
+    int64_t dir_begin;
+    double nu;
+    const double *mean, *inv_std, *state0;
+    double *returns, *traj, *final_state, *moments;
+    int32_t *status;
+};
+
+// What a rollout launch of the ARS pipeline is asked to carry besides its rollouts: the progress flag and the
+// covariance pass over the previous iteration's trajectories (cov_traj == nullptr: none).  The launch function
+// makes the kernels' SideJob (swimmer_cov.h) of it.
+struct SideWork {
+    uint32_t *flag;
+    uint32_t flag_value;
+    const double *cov_traj;
+    double *cov_acc;
+    int64_t cov_rolls;
+    int32_t cov_H;
+};
+
+// Tiling of a covariance pass over traj [H][D][n_roll] for workgroups of `block` threads:
+// nbx tiles of `block` rollouts x ny tiles of tchunk steps.  A function of (n_roll, H, block)
+// only, so a pass always sums in the same order (bit-reproducible results).
+struct CovTiling {
+    uint32_t nbx, ny;
+    int32_t tchunk;
+};
+
+// riding: the pass rides along in a rollout launch (or is the flush of a pass owed to one: same tiling,
+// same order of summation).  Otherwise it is the standalone pass of sw_traj_moments_f64, alone on the chip.
+CovTiling cov_tiling(int64_t n_roll, int32_t H, int block, int D, bool riding);   // swimmer_cov.hip
+int launch_traj_moments(const sw_params *p, int64_t n_roll, int32_t H, const double *traj, double *acc, int block,
+                        bool riding, void *stream);
+
+// One launch function per form, in the file of the form's kernels; they return launch_status(), or
+// SW_ERR_SEGMENTS for an n the form has no kernel for.  The entry points have validated the parameters and the
+// sizes, and cleared stale errors, already.
+// Rollouts (launch_rollouts, swimmer_abi.hip); side: pipeline only, and not for the lane form
+// (RolloutPlan::carries_side).
+using RolloutLauncher = int(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H,
+                            const RolloutArgs &a, hipStream_t stream, const SideWork *side);
+RolloutLauncher launch_oct3, launch_quad3, launch_row, launch_lane;
+// The ARS simulator gate (sw_ars_gate_f64): a = the ARS rollouts' arguments without trajectories / moments.
+using GateLauncher = int(const sw_params *sim, const RolloutPlan &plan, int64_t n_roll, int32_t H,
+                         const RolloutArgs &a, double gate_thr, int32_t *admit, hipStream_t stream);
+GateLauncher launch_gate_oct3, launch_gate_quad3, launch_gate_row, launch_gate_lane;
+// Safe exploration (sw_safe_rollouts_f64); there is no safe quad kernel.
+using SafeLauncher = int(const sw_params *real, const sw_params *sim, const RolloutPlan &plan, int64_t n_roll,
+                         int32_t H, const double *policies, int32_t cost_kind, int32_t cost_index, double sim_thresh,
+                         double real_thresh, double *returns, double *traj, int32_t *first_refused,
+                         int32_t *violations, int32_t *status, hipStream_t stream);
+SafeLauncher launch_safe_oct3, launch_safe_row, launch_safe_lane;
+
+}  // namespace sw_launch

@@ -1,0 +1,211 @@
+// swimmer_rollout_lane.hip -- rollouts with ONE ROLLOUT PER LANE (any n, either model): the throughput form for
+// batches that fill the chip, with its ARS gate and safe-exploration kernels.
+#include "swimmer_launch.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------
+// Rollouts.  ARS = false: policies[r][m][d] given per rollout.  ARS = true: rollout r is
+// direction dir_begin + (r >> 1) with sign + (r even) / - (r odd); its policy
+// P +- nu * delta is built here (ars_agent.py:141-142), so the perturbed policies never
+// exist in HBM.  The V2 whitening P diag(inv_std) (ars/environment.py:32-33) is folded into
+// the register copy of the policy once per rollout instead of once per step.
+template <int N, bool ARS, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+rollout_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+               const double *__restrict__ deltas, int64_t dir_begin, double nu,
+               const double *__restrict__ mean, const double *__restrict__ inv_std,
+               const double *__restrict__ state0, double *__restrict__ returns,
+               double *__restrict__ traj, double *__restrict__ final_state,
+               double *__restrict__ moments, int32_t *__restrict__ status)
+{
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
+
+// The ARS simulator gate (sw_ars_gate_f64) in the lane form: one rollout per lane, any n, either model.
+// The body is rollout_kernel's (swimmer_rollout_lane.inc) with ARS on, no trajectories / final state /
+// moments, and the decision (gate_store) in place of the plain return store.
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                const double *__restrict__ mean, const double *__restrict__ inv_std, double gate_thr,
+                int32_t *__restrict__ admit, double *__restrict__ returns, int32_t *__restrict__ status)
+{
+    constexpr bool ARS = true;
+    const double *const state0 = nullptr;
+    double *const traj = nullptr;
+    double *const final_state = nullptr;
+    double *const moments = nullptr;
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
+
+// ------------------------------------------------------------------------------------
+// Safe exploration (safe_ars/ars.py:101-153): every real step of a rollout is gated by a ONE-STEP look-ahead in a
+// simulator -- `isSafe` = sim_env.set_state(obs) + sim_env.step(action) + cost(sim obs) <= sim_thresh (:111-122,
+// called at :141).  One rollout per lane, the whole H-step loop in one launch: per step the action (policy @ obs,
+// :139), one Euler step with the SIMULATOR's constants on a copy of the state, the cost of where that lands, and --
+// if the gate is open -- the real step.  A refused step leaves the real env where it is (:150-151), so the same
+// action is proposed and refused for the rest of the horizon: the lane stops stepping and only repeats its state
+// into the trajectory.  Costs (include/swimmer_hip.h SW_COST_*): |obs[j]|, or max_i |thetadot_i| (the reference's
+// own experiment, safe_ars/experiment.py:45).
+template <int N>
+__device__ __forceinline__ double safe_cost(int32_t kind, int32_t index, double gdx, double gdy,
+                                            const double (&th)[N], const double (&thd)[N])
+{
+    if (kind == SW_COST_MAX_ABS_THETADOT) {
+        double c = fabs(thd[0]);
+#pragma unroll
+        for (int i = 1; i < N; ++i) c = fmax(c, fabs(thd[i]));   // np.max: NaN handled by the caller's <= test
+        bool nan = false;
+#pragma unroll
+        for (int i = 0; i < N; ++i) nan = nan || (thd[i] != thd[i]);
+        return nan ? __builtin_nan("") : c;                      // np.max propagates NaN, fmax would drop it
+    }
+    double v = (index == 0) ? gdx : gdy;                         // |obs[index]|, obs = [Gdx, Gdy, th_1, thd_1, ...]
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        v = (index == 2 + 2 * i) ? th[i] : v;
+        v = (index == 3 + 2 * i) ? thd[i] : v;
+    }
+    return fabs(v);
+}
+
+template <int N>
+__global__ void __launch_bounds__(kRollBlock)
+safe_rollout_kernel(sw::Consts Creal, sw::Consts Csim, int64_t n_roll, int32_t H,
+                    const double *__restrict__ policies, int32_t cost_kind, int32_t cost_index,
+                    double sim_thresh, double real_thresh, double *__restrict__ returns,
+                    double *__restrict__ traj, int32_t *__restrict__ first_refused,
+                    int32_t *__restrict__ violations, int32_t *__restrict__ status)
+{
+    constexpr int D = 2 * N + 2, M = N - 1;
+    const int64_t r = (int64_t)blockIdx.x * kRollBlock + threadIdx.x;
+    if (r >= n_roll) return;
+    double W[M][D];
+    const double *pl = policies + r * (M * D);
+#pragma unroll
+    for (int i = 0; i < M; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) W[i][j] = pl[i * D + j];
+    double gdx = 0.0, gdy = 0.0, th[N], thd[N];      // real_env.reset() (:133)
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        th[i] = kHalfPi;
+        thd[i] = 0.0;
+    }
+    auto record = [&](int32_t t) {
+        double *tp = traj + (int64_t)t * D * n_roll + r;
+        tp[0] = gdx;
+        tp[n_roll] = gdy;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            tp[(int64_t)(2 + 2 * i) * n_roll] = th[i];
+            tp[(int64_t)(3 + 2 * i) * n_roll] = thd[i];
+        }
+    };
+    double total = 0.0, thmax = 0.0;
+    bool ok = true;
+    int32_t refused_at = H, over = 0;
+    for (int32_t t = 0; t < H; ++t) {
+        thmax = sw::track_angle_range<N>(thmax, th);
+        double sm[D];
+        sm[0] = gdx;
+        sm[1] = gdy;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            sm[2 + 2 * i] = th[i];
+            sm[3 + 2 * i] = thd[i];
+        }
+        double u[M];                                  // ac = policy @ obs (:139)
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            double a0 = W[i][0] * sm[0], a1 = W[i][1] * sm[1];
+#pragma unroll
+            for (int j = 2; j < D; j += 2) {
+                a0 = __builtin_fma(W[i][j], sm[j], a0);
+                a1 = __builtin_fma(W[i][j + 1], sm[j + 1], a1);
+            }
+            u[i] = a0 + a1;
+        }
+        // the simulator's look-ahead from the real state (:120-121)
+        double sgx = gdx, sgy = gdy, sth[N], sthd[N], srew;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            sth[i] = th[i];
+            sthd[i] = thd[i];
+        }
+        (void)sw::euler_step<N>(Csim, sgx, sgy, sth, sthd, u, srew);
+        if (!(safe_cost<N>(cost_kind, cost_index, sgx, sgy, sth, sthd) <= sim_thresh)) {   // :122, NaN refuses
+            refused_at = t;
+            break;
+        }
+        double rew;
+        ok = sw::euler_step<N>(Creal, gdx, gdy, th, thd, u, rew) && ok;                     // :142
+        total += rew;
+        over += (safe_cost<N>(cost_kind, cost_index, gdx, gdy, th, thd) > real_thresh) ? 1 : 0;   // :143-144
+        if (traj) record(t);
+    }
+    if (traj)
+        for (int32_t t = refused_at; t < H; ++t) record(t);      // :151: the unchanged state, step after step
+    bool fin = isfinite(gdx) && isfinite(gdy);
+#pragma unroll
+    for (int i = 0; i < N; ++i) fin = fin && isfinite(th[i]) && isfinite(thd[i]);
+    const bool in_range = thmax < sw::kAngleLimit;
+    returns[r] = in_range ? total : __builtin_nan("");
+    if (first_refused) first_refused[r] = refused_at;
+    if (violations) violations[r] = over;
+    if (status)
+        status[r] = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) | (in_range ? 0 : SW_STATUS_RANGE);
+}
+
+}  // namespace
+
+namespace sw_launch __attribute__((visibility("hidden"))) {
+
+int launch_lane(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H, const RolloutArgs &a,
+                hipStream_t stream, const SideWork *)
+{
+    const sw::Consts C = make_consts(p);
+    const sw::TwinConsts T = make_twin_consts(p);
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto ARS, auto TWIN) {
+        hipLaunchKernelGGL((rollout_kernel<N.value, ARS.value, TWIN.value>), dim3(plan.rollout_blocks),
+                           dim3(plan.block), 0, stream, C, T, n_roll, H, a.policies, a.deltas, a.dir_begin,
+                           a.nu, a.mean, a.inv_std, a.state0, a.returns, a.traj, a.final_state, a.moments,
+                           a.status);
+    }, ars, is_twin(p));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_gate_lane(const sw_params *sim, const RolloutPlan &plan, int64_t n_roll, int32_t H, const RolloutArgs &a,
+                     double gate_thr, int32_t *admit, hipStream_t stream)
+{
+    const sw::Consts C = make_consts(sim);
+    const sw::TwinConsts T = make_twin_consts(sim);
+    const bool known_n = with_n<2, 8>(sim->n, [&](auto N, auto TWIN) {
+        hipLaunchKernelGGL((ars_gate_kernel<N.value, TWIN.value>), dim3(plan.rollout_blocks), dim3(plan.block), 0,
+                           stream, C, T, n_roll, H, a.policies, a.deltas, a.dir_begin, a.nu, a.mean, a.inv_std,
+                           gate_thr, admit, a.returns, a.status);
+    }, is_twin(sim));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_safe_lane(const sw_params *real, const sw_params *sim, const RolloutPlan &plan, int64_t n_roll, int32_t H,
+                     const double *policies, int32_t cost_kind, int32_t cost_index, double sim_thresh,
+                     double real_thresh, double *returns, double *traj, int32_t *first_refused, int32_t *violations,
+                     int32_t *status, hipStream_t stream)
+{
+    const sw::Consts Cr = make_consts(real), Cs = make_consts(sim);
+    const bool known_n = with_n<2, 8>(real->n, [&](auto N) {
+        hipLaunchKernelGGL((safe_rollout_kernel<N.value>), dim3(plan.rollout_blocks), dim3(plan.block), 0, stream, Cr,
+                           Cs, n_roll, H, policies, cost_kind, cost_index, sim_thresh, real_thresh, returns, traj,
+                           first_refused, violations, status);
+    });
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+}  // namespace sw_launch

@@ -1,4 +1,4 @@
-// Body of rollout_kernel (csrc/swimmer_kernels.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
+// Body of rollout_kernel (csrc/swimmer_rollout_lane.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
 // kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for token what it was) or 1 (the gate).
     constexpr int D = 2 * N + 2, M = N - 1;
     const int64_t r = (int64_t)blockIdx.x * kRollBlock + threadIdx.x;

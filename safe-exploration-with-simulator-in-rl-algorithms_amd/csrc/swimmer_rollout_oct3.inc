@@ -1,4 +1,4 @@
-// Body of rollout_oct3_kernel (csrc/swimmer_kernels.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
+// Body of rollout_oct3_kernel (csrc/swimmer_rollout_n3.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
 // kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for token what it was) or 1 (the gate).
     side_flag(side);
     if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)

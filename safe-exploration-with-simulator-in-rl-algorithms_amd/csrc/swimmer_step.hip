@@ -1,0 +1,537 @@
+// swimmer_step.hip -- one physics step for a batch of environments: step / accelerations / reset, the estimator's
+// residual kernels (one parameter set or a population), the batch-1 environment (sw_env1), and their entry points.
+#include <cstring>
+#include <new>
+
+#include "swimmer_launch.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------
+// TWIN selects the reference's native model (swimmer_twin.h) instead of the Gym model.
+// NT = nontemporal loads and stores: for batches that stream through HBM (larger than the
+// 256 MiB Infinity Cache) they measured +6..8 % (16.8 M envs: 5.91 -> 6.37 TB/s); smaller
+// batches keep plain accesses so that a step loop stays cache resident.
+template <bool NT> __device__ __forceinline__ double ld_f64(const double *p)
+{
+    return NT ? __builtin_nontemporal_load(p) : *p;
+}
+template <bool NT> __device__ __forceinline__ void st_f64(double v, double *p)
+{
+    if (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+#define SW_LD(p) ld_f64<NT>(p)
+#define SW_ST(v, p) st_f64<NT>(v, p)
+
+template <int N, bool TWIN, bool NT>
+__global__ void __launch_bounds__(kStepBlock)
+step_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restrict__ sin_,
+            const double *__restrict__ act, double *__restrict__ sout,
+            double *__restrict__ reward, int32_t *__restrict__ status)
+{
+    constexpr int M = N - 1;
+    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    if (e >= n_env) return;
+    double gdx = SW_LD(&sin_[e]), gdy = SW_LD(&sin_[n_env + e]);
+    double th[N], thd[N], u[M];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
+        thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
+    double r;
+    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+    const bool ok = TWIN ? sw::twin_step<N>(T, gdx, gdy, th, thd, u, r)
+                         : sw::euler_step<N>(C, gdx, gdy, th, thd, u, r);
+    if (!in_range) {   // outside sincos_fast's range: NaN out, SW_STATUS_RANGE
+        gdx = gdy = r = __builtin_nan("");
+#pragma unroll
+        for (int i = 0; i < N; ++i) th[i] = thd[i] = __builtin_nan("");
+    }
+    SW_ST(gdx, &sout[e]);
+    SW_ST(gdy, &sout[n_env + e]);
+    bool fin = isfinite(gdx) && isfinite(gdy);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        SW_ST(th[i], &sout[(int64_t)(2 + 2 * i) * n_env + e]);
+        SW_ST(thd[i], &sout[(int64_t)(3 + 2 * i) * n_env + e]);
+        fin = fin && isfinite(th[i]) && isfinite(thd[i]);
+    }
+    if (reward) SW_ST(r, &reward[e]);
+    if (status)
+        status[e] = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) |
+                    (in_range ? 0 : SW_STATUS_RANGE);
+}
+
+// One physics step per stored transition, COMPARED with the stored next state instead of written out: the
+// estimator's objective I(x) (ars/estimator.py:36-62) is the sum over every stored transition of
+// || sim_step(s_t, a_t) - s_{t+1} ||_2.  Reads state + action + stored next state (16 d + 8 m bytes per transition),
+// writes ONE double per workgroup: the fixed-order sum of its transitions' distances (lanes by shuffle tree, the four
+// waves in order) -- deterministic, and the d doubles per transition the step kernel would store, the difference
+// kernel would read back and the norm kernel would reduce never exist.  Out-of-range angles give NaN (as in step_kernel).
+template <int N, bool NT>
+__global__ void __launch_bounds__(kStepBlock)
+step_residual_kernel(sw::Consts C, int64_t n_env, const double *__restrict__ sin_, const double *__restrict__ act,
+                     const double *__restrict__ next_ref, double *__restrict__ partial)
+{
+    constexpr int M = N - 1;
+    __shared__ double wsum[kStepBlock / kWave];
+    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    double dist = 0.0;
+    if (e < n_env) {
+        double gdx = SW_LD(&sin_[e]), gdy = SW_LD(&sin_[n_env + e]);
+        double th[N], thd[N], u[M];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
+            thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
+        }
+#pragma unroll
+        for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
+        // the stored next state: its loads are in flight while the step is computed
+        double rx = SW_LD(&next_ref[e]), ry = SW_LD(&next_ref[n_env + e]), rth[N], rthd[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            rth[i] = SW_LD(&next_ref[(int64_t)(2 + 2 * i) * n_env + e]);
+            rthd[i] = SW_LD(&next_ref[(int64_t)(3 + 2 * i) * n_env + e]);
+        }
+        const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+        double r;
+        (void)sw::euler_step<N>(C, gdx, gdy, th, thd, u, r);
+        double q = (gdx - rx) * (gdx - rx);
+        q = __builtin_fma(gdy - ry, gdy - ry, q);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            q = __builtin_fma(th[i] - rth[i], th[i] - rth[i], q);
+            q = __builtin_fma(thd[i] - rthd[i], thd[i] - rthd[i], q);
+        }
+        dist = in_range ? sqrt(q) : __builtin_nan("");
+    }
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
+    if (threadIdx.x % kWave == 0) wsum[threadIdx.x / kWave] = dist;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = wsum[0];
+#pragma unroll
+        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[w];
+        partial[blockIdx.x] = t;
+    }
+}
+
+// The same objective for a POPULATION of parameter sets (the CMA-ES generation of the estimator's search): each
+// workgroup reads its 256 transitions ONCE into registers and steps a copy of every state for each candidate of its
+// group (blockIdx.y: candidates [y * kPopGroup, ...)).  Per candidate everything is step_residual_kernel's: the same
+// partition, the same consts (sw::consts_of, here from the candidate's l_i, m_i, k), euler_step, the same FMA chain, the
+// same lane tree and wave order -- partial[j][b] has the bits step_residual_kernel gives for candidate j.  A candidate
+// that breaks validate_params' rule gets NaN partials and SW_STATUS_PARAM; its neighbours do not notice.
+template <int N, bool NT>
+__global__ void __launch_bounds__(kStepBlock)
+step_residual_pop_kernel(sw::Consts base, int64_t n_cand, const double *__restrict__ cand, int64_t n_env,
+                         const double *__restrict__ sin_, const double *__restrict__ act,
+                         const double *__restrict__ next_ref, double *__restrict__ partial,
+                         int32_t *__restrict__ cand_status)
+{
+    constexpr int M = N - 1;
+    __shared__ sw::Consts cc[kPopGroup];
+    __shared__ int cok[kPopGroup];
+    __shared__ double wsum[kPopGroup][kStepBlock / kWave];
+    const int64_t j0 = (int64_t)blockIdx.y * kPopGroup;
+    const int nc = (int)(n_cand - j0 < kPopGroup ? n_cand - j0 : kPopGroup);
+    if ((int)threadIdx.x < nc) {
+        const double *x = cand + (j0 + threadIdx.x) * 3;   // [l_i, m_i, k]
+        const double l = x[0], m = x[1], k = x[2];
+        const bool ok = l > 0.0 && m > 0.0 && isfinite(l) && isfinite(m) && isfinite(k);
+        cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
+        cok[threadIdx.x] = ok;
+        if (cand_status && blockIdx.x == 0) cand_status[j0 + threadIdx.x] = ok ? SW_STATUS_OK : SW_STATUS_PARAM;
+    }
+    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    const bool live = e < n_env;
+    double gdx = 0.0, gdy = 0.0, th[N], thd[N], u[M], rx = 0.0, ry = 0.0, rth[N], rthd[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) th[i] = thd[i] = rth[i] = rthd[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) u[i] = 0.0;
+    if (live) {
+        gdx = SW_LD(&sin_[e]);
+        gdy = SW_LD(&sin_[n_env + e]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
+            thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
+        }
+#pragma unroll
+        for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
+        rx = SW_LD(&next_ref[e]);
+        ry = SW_LD(&next_ref[n_env + e]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            rth[i] = SW_LD(&next_ref[(int64_t)(2 + 2 * i) * n_env + e]);
+            rthd[i] = SW_LD(&next_ref[(int64_t)(3 + 2 * i) * n_env + e]);
+        }
+    }
+    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+    __syncthreads();
+#pragma unroll 1
+    for (int c = 0; c < nc; ++c) {
+        double dist = 0.0;
+        if (live) {
+            double x = gdx, y = gdy, t[N], td[N], r;
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                t[i] = th[i];
+                td[i] = thd[i];
+            }
+            (void)sw::euler_step<N>(cc[c], x, y, t, td, u, r);
+            double q = (x - rx) * (x - rx);
+            q = __builtin_fma(y - ry, y - ry, q);
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                q = __builtin_fma(t[i] - rth[i], t[i] - rth[i], q);
+                q = __builtin_fma(td[i] - rthd[i], td[i] - rthd[i], q);
+            }
+            dist = (in_range && cok[c]) ? sqrt(q) : __builtin_nan("");
+        }
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
+        if (threadIdx.x % kWave == 0) wsum[c][threadIdx.x / kWave] = dist;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nc) {
+        double t = wsum[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
+        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// value[j] = the sum of row j of partial [n_cand][nb] in ONE fixed order: lane l adds b = l, l + 64, l + 128, ... in
+// turn (starting from 0.0), then the 64 lane sums go through the shuffle tree.  One wave per candidate.
+__global__ void __launch_bounds__(kWave)
+residual_rows_sum_kernel(int64_t nb, const double *__restrict__ partial, double *__restrict__ value)
+{
+    const double *row = partial + (int64_t)blockIdx.x * nb;
+    double t = 0.0;
+    for (int64_t b = threadIdx.x; b < nb; b += kWave) t += row[b];
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) t += __shfl_down(t, off, kWave);
+    if (threadIdx.x == 0) value[blockIdx.x] = t;
+}
+
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kStepBlock)
+accel_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restrict__ sin_,
+             const double *__restrict__ act, double *__restrict__ gdd, double *__restrict__ tdd)
+{
+    constexpr int M = N - 1;
+    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    if (e >= n_env) return;
+    double gdx = sin_[e], gdy = sin_[n_env + e];
+    double th[N], thd[N], u[M], a[N], ax, ay;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        th[i] = sin_[(int64_t)(2 + 2 * i) * n_env + e];
+        thd[i] = sin_[(int64_t)(3 + 2 * i) * n_env + e];
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) u[i] = act[(int64_t)i * n_env + e];
+    if (TWIN) sw::accelerations_twin<N>(T, gdx, gdy, th, thd, u, ax, ay, a);
+    else sw::accelerations<N>(C, gdx, gdy, th, thd, u, ax, ay, a);
+    if (!(sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit)) {
+        ax = ay = __builtin_nan("");
+#pragma unroll
+        for (int i = 0; i < N; ++i) a[i] = __builtin_nan("");
+    }
+    gdd[e] = ax;
+    gdd[n_env + e] = ay;
+#pragma unroll
+    for (int i = 0; i < N; ++i) tdd[(int64_t)i * n_env + e] = a[i];
+}
+
+// Gym reset: Gdot = 0, theta = pi/2, thetadot = 0 (remy_swimmer_env.py:64-66); the native
+// twin's env_start sets every observation entry to 0.001 (SwimmerEnvironment.cpp:39-42).
+__global__ void reset_kernel(int n, int twin, int64_t n_env, double *__restrict__ state)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_env) return;
+    state[e] = twin ? kTwinStart : 0.0;
+    state[n_env + e] = twin ? kTwinStart : 0.0;
+    for (int i = 0; i < n; ++i) {
+        state[(int64_t)(2 + 2 * i) * n_env + e] = twin ? kTwinStart : kHalfPi;
+        state[(int64_t)(3 + 2 * i) * n_env + e] = twin ? kTwinStart : 0.0;
+    }
+}
+
+// One swimmer handed over in HOST memory (sw_env1, the batch-1 drop-in surfaces).  io = the
+// handle's pinned, device-mapped block (SW_ENV1_* offsets).  One wave: lane l pulls double l of
+// [state | action] -- ONE read burst over the bus instead of 25 round trips -- every lane then
+// runs the same step on broadcast copies, lane 0 posts the results and, behind a system-scope
+// fence, the sequence number the host spins on.
+template <int N, bool TWIN, bool ACCEL>
+__global__ void __launch_bounds__(kWave)
+env1_kernel(sw::Consts C, sw::TwinConsts T, double *__restrict__ io, int32_t *__restrict__ status,
+            uint32_t *__restrict__ seq_flag, uint32_t seq)
+{
+    constexpr int D = 2 * N + 2, M = N - 1;
+    const int lane = threadIdx.x;
+    const double mine = (lane < SW_ENV1_ACTION + M) ? io[lane] : 0.0;   // state 0..17, action 18..24
+    double gdx = __shfl(mine, 0, kWave), gdy = __shfl(mine, 1, kWave);
+    double th[N], thd[N], u[M > 0 ? M : 1];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        th[i] = __shfl(mine, 2 + 2 * i, kWave);
+        thd[i] = __shfl(mine, 3 + 2 * i, kWave);
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) u[i] = __shfl(mine, SW_ENV1_ACTION + i, kWave);
+    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+    if (ACCEL) {
+        double ax, ay, a[N];
+        if (TWIN) sw::accelerations_twin<N>(T, gdx, gdy, th, thd, u, ax, ay, a);
+        else sw::accelerations<N>(C, gdx, gdy, th, thd, u, ax, ay, a);
+        if (lane == 0) {
+            io[SW_ENV1_GDD] = in_range ? ax : __builtin_nan("");
+            io[SW_ENV1_GDD + 1] = in_range ? ay : __builtin_nan("");
+#pragma unroll
+            for (int i = 0; i < N; ++i) io[SW_ENV1_TDD + i] = in_range ? a[i] : __builtin_nan("");
+        }
+    } else {
+        double r;
+        const bool ok = TWIN ? sw::twin_step<N>(T, gdx, gdy, th, thd, u, r)
+                             : sw::euler_step<N>(C, gdx, gdy, th, thd, u, r);
+        if (!in_range) {
+            gdx = gdy = r = __builtin_nan("");
+#pragma unroll
+            for (int i = 0; i < N; ++i) th[i] = thd[i] = __builtin_nan("");
+        }
+        bool fin = isfinite(gdx) && isfinite(gdy);
+#pragma unroll
+        for (int i = 0; i < N; ++i) fin = fin && isfinite(th[i]) && isfinite(thd[i]);
+        if (lane == 0) {
+            io[SW_ENV1_NEXT] = gdx;
+            io[SW_ENV1_NEXT + 1] = gdy;
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                io[SW_ENV1_NEXT + 2 + 2 * i] = th[i];
+                io[SW_ENV1_NEXT + 3 + 2 * i] = thd[i];
+            }
+            io[SW_ENV1_REWARD] = r;
+            *status = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) |
+                      (in_range ? 0 : SW_STATUS_RANGE);
+        }
+    }
+    static_assert(D <= SW_ENV1_ACTION && SW_ENV1_ACTION + M <= SW_ENV1_NEXT && SW_ENV1_NEXT + D <= SW_ENV1_REWARD,
+                  "I/O block layout");
+    if (lane == 0) {
+        __threadfence_system();   // the results are visible to the host before the sequence number is
+        __hip_atomic_store(seq_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// Batches beyond the Infinity Cache stream through HBM: the step kernels' NT (nontemporal) forms.
+bool streams_through_hbm(const sw_params *p, int64_t n_env)
+{
+    const int d = 2 * p->n + 2;
+    return n_env * (int64_t)(8 * (2 * d + p->n)) > kStepStreamBytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_reset_f64(const sw_params *p, int64_t n_env, double *state, void *stream)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!state) return SW_ERR_NULL;
+    if (n_env < 0) return SW_ERR_SIZE;
+    if (n_env == 0) return SW_OK;
+    const unsigned grid = (unsigned)((n_env + 255) / 256);
+    hipLaunchKernelGGL(reset_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p->n,
+                       is_twin(p) ? 1 : 0, n_env, state);
+    return launch_status();
+}
+
+int sw_step_f64(const sw_params *p, int64_t n_env, const double *state_in, const double *action,
+                double *state_out, double *reward, int32_t *status, void *stream)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_env < 0) return SW_ERR_SIZE;
+    if (n_env == 0) return SW_OK;
+    if (!state_in || !action || !state_out) return SW_ERR_NULL;
+    const sw::Consts C = make_consts(p);
+    const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
+    const sw::TwinConsts T = make_twin_consts(p);
+    bool nt = streams_through_hbm(p, n_env);
+    static const char *nt_env = getenv("SWIMMER_STEP_NT");   // measurement knob: "0" / "1" force it
+    if (nt_env && (nt_env[0] == '0' || nt_env[0] == '1')) nt = nt_env[0] == '1';
+    auto launch = [&](auto *kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kStepBlock), 0, (hipStream_t)stream, C, T, n_env, state_in,
+                           action, state_out, reward, status);
+    };
+    // (the twin model has no nontemporal form)
+    const bool known_n =
+        is_twin(p) ? with_n<2, 8>(p->n, [&](auto N) { launch(step_kernel<N.value, true, false>); })
+                   : with_n<2, 8>(p->n, [&](auto N, auto NT) { launch(step_kernel<N.value, false, NT.value>); }, nt);
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int sw_step_residual_f64(const sw_params *p, int64_t n_env, const double *state, const double *action,
+                         const double *next_ref, double *partial, void *stream)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (is_twin(p)) return SW_ERR_PARAM;          // the estimator's objective is defined on the Gym model
+    if (n_env < 0) return SW_ERR_SIZE;
+    if (n_env == 0) return SW_OK;
+    if (!state || !action || !next_ref || !partial) return SW_ERR_NULL;
+    const sw::Consts C = make_consts(p);
+    const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto NT) {
+        hipLaunchKernelGGL((step_residual_kernel<N.value, NT.value>), dim3(grid), dim3(kStepBlock), 0,
+                           (hipStream_t)stream, C, n_env, state, action, next_ref, partial);
+    }, streams_through_hbm(p, n_env));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double *cand, int64_t n_env,
+                             const double *state, const double *action, const double *next_ref, double *partial,
+                             double *value, int32_t *cand_status, void *stream)
+{
+    int rc = check_params(base);
+    if (rc) return rc;
+    if (!cand || !state || !action || !next_ref || !partial) return SW_ERR_NULL;
+    if (n_cand < 1 || n_cand > kPopMaxCandidates || n_env < 0) return SW_ERR_SIZE;
+    if (is_twin(base)) return SW_ERR_PARAM;
+    if (n_env == 0) return SW_OK;
+    const sw::Consts C = make_consts(base);    // h and the direction; l_i, m_i, k come from each candidate
+    const int64_t nb = (n_env + kStepBlock - 1) / kStepBlock;
+    const dim3 grid((unsigned)nb, (unsigned)((n_cand + kPopGroup - 1) / kPopGroup));
+    const bool known_n = with_n<2, 8>(base->n, [&](auto N, auto NT) {
+        hipLaunchKernelGGL((step_residual_pop_kernel<N.value, NT.value>), grid, dim3(kStepBlock), 0,
+                           (hipStream_t)stream, C, n_cand, cand, n_env, state, action, next_ref, partial,
+                           cand_status);
+    }, streams_through_hbm(base, n_env));
+    if (!known_n) return SW_ERR_SEGMENTS;
+    if (value) {
+        rc = launch_status();
+        if (rc) return rc;
+        hipLaunchKernelGGL(residual_rows_sum_kernel, dim3((unsigned)n_cand), dim3(kWave), 0, (hipStream_t)stream, nb,
+                           partial, value);
+    }
+    return launch_status();
+}
+
+int64_t sw_step_residual_blocks(int64_t n_env) { return n_env <= 0 ? 0 : (n_env + kStepBlock - 1) / kStepBlock; }
+
+int sw_accel_f64(const sw_params *p, int64_t n_env, const double *state, const double *action,
+                 double *gdd, double *tdd, void *stream)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_env < 0) return SW_ERR_SIZE;
+    if (n_env == 0) return SW_OK;
+    if (!state || !action || !gdd || !tdd) return SW_ERR_NULL;
+    const sw::Consts C = make_consts(p);
+    const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
+    const sw::TwinConsts T = make_twin_consts(p);
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
+        hipLaunchKernelGGL((accel_kernel<N.value, TWIN.value>), dim3(grid), dim3(kStepBlock), 0,
+                           (hipStream_t)stream, C, T, n_env, state, action, gdd, tdd);
+    }, is_twin(p));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+// ---- one swimmer per call (include/swimmer_hip.h, sw_env1) -----------------------------
+struct sw_env1 {
+    double *io_host = nullptr, *io_dev = nullptr;   // SW_ENV1_DOUBLES doubles + {status, seq}
+    hipStream_t stream = nullptr;
+    uint32_t seq = 0;
+    int device = 0;   // the device that was current at sw_env1_create: every launch goes there
+};
+
+int sw_env1_create(sw_env1 **out)
+{
+    if (!out) return SW_ERR_NULL;
+    sw_env1 *e = new (std::nothrow) sw_env1();
+    if (!e) return SW_ERR_LAUNCH;
+    const size_t bytes = sizeof(double) * SW_ENV1_DOUBLES + 64;
+    bool ok = hipGetDevice(&e->device) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&e->io_host, bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+    if (ok) {
+        memset(e->io_host, 0, bytes);
+        ok = hipHostGetDevicePointer((void **)&e->io_dev, e->io_host, 0) == hipSuccess &&
+             hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) == hipSuccess;
+        // (normal priority: a batch-1 step has nothing to overtake)
+    }
+    if (!ok) {
+        sw_env1_destroy(e);
+        return SW_ERR_LAUNCH;
+    }
+    *out = e;
+    return SW_OK;
+}
+
+void sw_env1_destroy(sw_env1 *e)
+{
+    if (!e) return;
+    if (e->stream) {
+        (void)hipStreamSynchronize(e->stream);
+        (void)hipStreamDestroy(e->stream);
+    }
+    if (e->io_host) (void)hipHostFree(e->io_host);
+    delete e;
+}
+
+double *sw_env1_io(sw_env1 *e) { return e ? e->io_host : nullptr; }
+
+static int env1_run(sw_env1 *e, const sw_params *p, bool accel, int32_t *status)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!e) return SW_ERR_NULL;
+    const sw::Consts C = make_consts(p);
+    const sw::TwinConsts T = make_twin_consts(p);
+    int32_t *st_host = reinterpret_cast<int32_t *>(e->io_host + SW_ENV1_DOUBLES);
+    int32_t *st_dev = reinterpret_cast<int32_t *>(e->io_dev + SW_ENV1_DOUBLES);
+    const volatile uint32_t *flag_host = reinterpret_cast<const volatile uint32_t *>(st_host + 1);
+    uint32_t *flag_dev = reinterpret_cast<uint32_t *>(st_dev + 1);
+    const uint32_t seq = ++e->seq;
+    // the handle's stream and mapped block belong to e->device: launch there whatever the caller's current
+    // device is, and leave the caller's current device as it was
+    int caller_device = e->device;
+    if (hipGetDevice(&caller_device) != hipSuccess) return SW_ERR_LAUNCH;
+    if (caller_device != e->device && hipSetDevice(e->device) != hipSuccess) return SW_ERR_LAUNCH;
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN, auto ACCEL) {
+        hipLaunchKernelGGL((env1_kernel<N.value, TWIN.value, ACCEL.value>), dim3(1), dim3(kWave), 0, e->stream, C, T,
+                           e->io_dev, st_dev, flag_dev, seq);
+    }, is_twin(p), accel);
+    rc = known_n ? launch_status() : SW_ERR_SEGMENTS;
+    if (caller_device != e->device) (void)hipSetDevice(caller_device);
+    if (rc) return rc;
+    for (int64_t spins = 0; *flag_host != seq; ++spins) {
+        if ((spins & 0xffff) == 0xffff) {
+            // not hot any more: a stream that has drained without the flag moving has failed
+            const hipError_t q = hipStreamQuery(e->stream);
+            if (q == hipSuccess) {
+                if (*flag_host == seq) break;
+                return SW_ERR_LAUNCH;
+            }
+            if (q != hipErrorNotReady) return SW_ERR_LAUNCH;
+        }
+        __builtin_ia32_pause();
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (status) *status = accel ? 0 : *st_host;
+    return SW_OK;
+}
+
+int sw_env1_step(sw_env1 *e, const sw_params *p, int32_t *status) { return env1_run(e, p, false, status); }
+int sw_env1_accel(sw_env1 *e, const sw_params *p) { return env1_run(e, p, true, nullptr); }
+
+}  // extern "C"

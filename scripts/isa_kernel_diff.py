@@ -6,23 +6,17 @@ Prints every kernel of OLD whose instruction text differs in NEW (or is missing 
 count.  Absolute addresses are ignored; branch offsets and everything else of an instruction are compared."""
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-LLVM = "/opt/rocm/lib/llvm/bin"
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import swimmer_amd  # noqa: E402
 
 
 def kernels(lib):
-    with tempfile.TemporaryDirectory() as tmp:
-        fat, elf = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "gfx950.elf")
-        subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={elf}"], check=True)
-        text = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", elf], check=True,
-                              capture_output=True, text=True).stdout
+    text = swimmer_amd._build.disassemble(lib)     # every gfx950 code object in the library
     out, cur = {}, None
-    for line in text.split("\n"):
+    for line in text:
         m = re.match(r"^[0-9a-f]+ <(.*)>:", line)
         if m:
             cur = out.setdefault(m.group(1), [])

@@ -2,10 +2,7 @@
 code object (design aid).  A lone wave issues a 4-byte instruction every ~1.85 ns and an 8-byte one
 every ~2.24 ns (scripts/ubench/f64_forms.hip), so the bytes are the cost.
 
-  hipcc --genco --offload-arch=gfx950 -O3 -std=c++17 csrc/swimmer_kernels.hip -o /tmp/k.hsaco
-  clang-offload-bundler --unbundle --type=o --input=/tmp/k.hsaco \
-        --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=/tmp/k.co
-  llvm-objdump -d /tmp/k.co > /tmp/k.dis
+  python -c "import swimmer_amd as sw; [print(l) for l in sw._build.disassemble(raw_insn=True)]" > /tmp/k.dis
   python scripts/isa_loop_bytes.py /tmp/k.dis rollout_quad3_kernelILb1ELb1ELb1E [steps_per_trip]
 """
 import collections

@@ -887,7 +887,7 @@ def test_basic_ars_mirror_vs_reference(sw, golden):
 @pytest.mark.parametrize("n", [4, 6, 7, 8])
 def test_violent_accelerations_inside_an_unchecked_trip(sw, n):
     """The row kernel (n = 4 ... 8) checks its reduced angles once per trip of FOUR steps, from |thetadot| at the
-    trip's START (csrc/swimmer_kernels.hip, `too_fast`): what thetadot GAINS inside the trip is not in that bound
+    trip's START (csrc/swimmer_rollout_row.inc, `too_fast`): what thetadot GAINS inside the trip is not in that bound
     (ADVICE r03).  Worst case for it: rollouts that start at rest (thetadot = 0: every first trip runs unchecked)
     under policies whose gains of 20 ... 100 produce joint torques of hundreds, i.e. angular accelerations of
     thousands of rad/s^2 -- an angle then travels 6 h^2 thetadotdot = 0.01 ... 0.1 rad inside ONE unchecked trip, up

@@ -1,8 +1,8 @@
 """Properties of the BUILT device code that the source can only ask for (read out of the library's gfx950
-code object, no GPU needed).
+code objects, no GPU needed).
 
 * The covariance pass hands a tile's row of partial sums to the merging workgroup through a ticket counter
-  (csrc/swimmer_kernels.hip, moments_tile).  The row is written with agent-scope write-through stores and the
+  (csrc/swimmer_cov.h, moments_tile).  The row is written with agent-scope write-through stores and the
   ticket must not become visible before those stores have completed: every wave waits `s_waitcnt vmcnt(0)`
   before the barrier behind which thread 0 takes the ticket.  A workgroup-scope release fence does not emit
   that wait on gfx950 (round 3 relied on it), so the test looks for the instruction itself: between the last
@@ -53,8 +53,8 @@ def _kernels(lines, fragment):
 
 
 @needs_tools
-def test_ticket_is_taken_after_the_tile_rows_stores_have_completed(tmp_path):
-    lines = _disassemble(tmp_path)
+def test_ticket_is_taken_after_the_tile_rows_stores_have_completed():
+    lines = _disassemble()
     seen = 0
     for fragment in TICKET_KERNELS:
         ks = _kernels(lines, fragment)
@@ -75,6 +75,6 @@ def test_ticket_is_taken_after_the_tile_rows_stores_have_completed(tmp_path):
 
 
 @needs_tools
-def test_no_matrix_instructions_in_the_product(tmp_path):
-    lines = _disassemble(tmp_path)
+def test_no_matrix_instructions_in_the_product():
+    lines = _disassemble()
     assert not [l for l in lines if re.match(r"\s+v_(s?mfma|wmma)", l)]

@@ -1,4 +1,4 @@
-"""Where the rollout kernels' hot loops sit inside their 64-byte code line (csrc/swimmer_kernels.hip,
+"""Where the rollout kernels' hot loops sit inside their 64-byte code line (csrc/swimmer_launch.h,
 SW_PIN_LOOP).  A lone wave's issue rate depends on it -- the same instructions ran 3.5 % (n = 3) to 11 %
 (n = 7) apart at different offsets -- and the offset of an unpinned loop moves with every unrelated edit
 earlier in the file.  This test reads the offsets out of the built library and compares them with the ones
@@ -17,6 +17,8 @@ import shutil
 import subprocess
 
 import pytest
+
+import swimmer_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "safe-exploration-with-simulator-in-rl-algorithms_amd", "csrc", "libswimmer_hip.so")
@@ -41,13 +43,9 @@ EXPECTED = {
 }
 
 
-def _disassemble(tmp_path):
-    fat, elf = str(tmp_path / "fat.bin"), str(tmp_path / "gfx950.elf")
-    subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", LIB, fat], check=True)
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={elf}"], check=True)
-    return subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", elf], check=True,
-                          capture_output=True, text=True).stdout.split("\n")
+def _disassemble():
+    """The disassembly of every gfx950 code object in the library (the one recipe: swimmer_amd._build.disassemble)."""
+    return swimmer_amd._build.disassemble(LIB)
 
 
 def _backward_loops(lines, fragment):
@@ -78,10 +76,10 @@ def _compiler():
 @pytest.mark.perf_lint
 @pytest.mark.skipif(not (os.path.exists(LIB) and shutil.which(f"{LLVM}/llvm-objdump")),
                     reason="needs the built library and the ROCm llvm tools")
-def test_hot_loops_sit_where_the_sweep_put_them(tmp_path):
+def test_hot_loops_sit_where_the_sweep_put_them():
     if PINNED_COMPILER not in _compiler():
         pytest.skip(f"the placement table belongs to hipcc {PINNED_COMPILER}; another compiler lays the loops out anew")
-    lines = _disassemble(tmp_path)
+    lines = _disassemble()
     moved = []
     for fragment, (body, where) in EXPECTED.items():
         all_loops = _backward_loops(lines, fragment)
