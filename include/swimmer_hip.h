@@ -21,6 +21,9 @@
  *                                                                   ars/ars_agent.py:144-157
  *   sw_ars_update_f64    ARSAgent.sort_directions / update_policy and the V2 statistics
  *                                                                   ars/ars_agent.py:97-130, :176-182
+ *   sw_ars_rollouts_multi_f64, sw_ars_update_multi_f64
+ *                        the same two for every seed of Experiment.plot at once (one Ray actor per seed in the
+ *                        reference)                                  ars/experiment.py:61-72
  *   sw_traj_moments_f64  np.mean / np.cov over the saved states     ars/ars_agent.py:180-182
  *   sw_env1_step         the same step for ONE swimmer handed over in host memory (the Gym
  *                        surface and the RL-Glue env_step, SwimmerEnvironment.cpp:53-68)
@@ -238,6 +241,43 @@ int sw_ars_update_f64(const sw_params *p, int64_t n_dir, const double *returns,
                       int64_t top_b, const double *moments, int64_t n_moment_rows,
                       double *running, int64_t n_new_states, double *mean, double *inv_std,
                       double *sigma_out, void *stream);
+
+/* ---- many agents in lock-step: one rollout launch and one update launch per iteration for ALL of them ----
+ * A learning curve is n_seed independent ARSAgents (ars/experiment.py:61-72, one Ray actor per seed).  With the
+ * reference's N = 1 .. a handful of directions one agent's iteration is a launch that leaves the chip idle, and the
+ * launches of different seeds are independent: these two entry points run them as one.
+ *
+ * sw_ars_rollouts_multi_f64: sw_ars_rollouts_f64 (dir_begin = 0, no trajectories) for n_agent agents that share
+ * p, n_dir, H and nu.  Every array is the single-agent array once per agent, agent-major and dense:
+ *   policy  : [n_agent][m][d]             deltas : [n_agent][n_dir][m][d]
+ *   mean, inv_std : [n_agent][d] each, or both NULL (V1)
+ *   returns : [n_agent][2 * n_dir]        entry 2j / 2j+1 of agent a = +/- rollout of ITS direction j
+ *   moments : NULL or [n_agent][sw_moments_blocks(2 * n_dir)][2d]; row i of agent a covers ITS rollouts
+ *             16i .. 16i+15, as in a single-agent launch: no row holds states of two agents
+ *   status  : NULL or [n_agent][2 * n_dir]
+ * Agent a's rollouts read agent a's policy, deltas, mean and inv_std only.  Inside the launch every agent's
+ * rollouts are padded to whole workgroups (16 rollout slots, 64 in the lane form); padding slots write nothing.
+ * The kernel form is chosen as sw_ars_rollouts_f64 chooses it, from n_agent * 16 * ceil(2 n_dir / 16) slots
+ * (SW_FLAG_ROLLOUT_* honoured); per rollout each form runs the instructions of its single-agent kernel, so a
+ * launch gives, agent by agent, the bits of sw_ars_rollouts_f64 in the same form.
+ * Errors, before any HIP call: NULL policy / deltas / returns, or one of mean / inv_std without the other:
+ * SW_ERR_NULL; n_agent < 1, n_dir < 1, H < 0, n_agent > 65535, n_dir > 2^23 or 2^32 threads and more: SW_ERR_SIZE;
+ * parameters as everywhere. */
+int sw_ars_rollouts_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, int32_t H,
+                              const double *policy, const double *deltas, double nu,
+                              const double *mean, const double *inv_std, double *returns,
+                              double *moments, int32_t *status, void *stream);
+
+/* sw_ars_update_f64 for n_agent agents in one launch.  returns [n_agent][2 * n_dir], deltas [n_agent][n_dir][m][d],
+ * policy [n_agent][m][d], moments [n_agent][n_moment_rows][2d], running [n_agent][1 + 2d], mean / inv_std
+ * [n_agent][d], sigma_out NULL or [n_agent]; alpha, b, top_b and n_new_states hold for every agent.  Each agent's
+ * result has the bits of a sw_ars_update_f64 call on its slices (the order of summation depends on n_dir only).
+ * Errors as sw_ars_update_f64, and n_agent < 1 or > 65535: SW_ERR_SIZE. */
+int sw_ars_update_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const double *returns,
+                            const double *deltas, double *policy, double alpha, double b,
+                            int64_t top_b, const double *moments, int64_t n_moment_rows,
+                            double *running, int64_t n_new_states, double *mean, double *inv_std,
+                            double *sigma_out, void *stream);
 
 /* The same update reading an all-gathered buffer in place (no repacking between the
  * collective and the update):  gathered = `world` segments of

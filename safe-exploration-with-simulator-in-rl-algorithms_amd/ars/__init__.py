@@ -1,3 +1,5 @@
 from .parameters import EnvParam, ARSParam, Threshold  # noqa: F401
 from .environment import Environment  # noqa: F401
 from .ars_agent import ARSAgent  # noqa: F401
+from .agent_batch import ARSAgentBatch  # noqa: F401
+from .experiment import Experiment  # noqa: F401

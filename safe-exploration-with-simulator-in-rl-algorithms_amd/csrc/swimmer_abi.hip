@@ -231,6 +231,37 @@ int sw_ars_gate_f64(const sw_params *sim, int64_t dir_begin, int64_t n_dir, int3
     return launch_gate_lane(sim, plan, n_roll, H, a, sim_thresh, admit, st);
 }
 
+// The ARS rollouts of n_agent agents (same model, same n_dir, same H) in one launch.  Every agent gets whole
+// workgroups: form_slots(form) * ceil(2 n_dir / form_slots(form)) rollout slots, so a workgroup's base pointers are
+// uniform and a moment row never holds two agents.  The form is chosen from the slot count of the WHOLE launch at the
+// 16-slot granule: that count is what decides whether a segment-per-lane kernel still finds an idle SIMD per wave.
+int sw_ars_rollouts_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, int32_t H, const double *policy,
+                              const double *deltas, double nu, const double *mean, const double *inv_std,
+                              double *returns, double *moments, int32_t *status, void *stream)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;
+    if (!policy || !deltas || !returns) return SW_ERR_NULL;
+    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
+    // grid.y carries the agent; an agent's rollouts are indexed like a single launch's
+    if (n_agent > 65535 || n_dir > ((int64_t)1 << 23)) return SW_ERR_SIZE;
+    const int64_t n_roll = 2 * n_dir;
+    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
+    const RolloutPlan plan = plan_rollouts(p, slots, H, false);
+    const dim3 grid = multi_grid(plan, n_agent, n_roll);
+    if ((int64_t)grid.x * grid.y * plan.block >= ((int64_t)1 << 32)) return SW_ERR_SIZE;   // threads of one launch
+    const MultiArgs a{policy, deltas, mean, inv_std, returns, moments, status};
+    const hipStream_t st = (hipStream_t)stream;
+    switch (plan.form) {
+    case Form::Oct3: return launch_multi_oct3(p, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Quad3: return launch_multi_quad3(p, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Row: return launch_multi_row(p, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Lane: break;
+    }
+    return launch_multi_lane(p, plan, n_agent, n_roll, H, a, nu, st);
+}
+
 // ---- ARS iteration pipeline ---------------------------------------------------------
 // Host-side enqueue logic of one ARS iteration in native code: the caller's stream (the
 // critical path: rollouts -> [all-gather] -> update), a copy stream for the H2D of the deltas,

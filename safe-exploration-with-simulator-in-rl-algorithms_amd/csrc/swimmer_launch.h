@@ -29,9 +29,18 @@
 //   rollout_kernel<N,ARS,TWIN> any n, ONE ROLLOUT PER LANE: the throughput form for batches that
 //                              fill the chip, and the only form of the twin model
 //   (each rollout file also holds its form's ARS gate and safe-exploration kernels)
+//   ars_multi_oct3_kernel<MOM>, ars_multi_quad3_kernel<MOM>, ars_multi_row_kernel<N,MOM>,
+//   ars_multi_lane_kernel<N,TWIN>  (one per form, in the form's file)
+//                              sw_ars_rollouts_multi_f64: the ARS rollouts of MANY AGENTS in one launch, grid
+//                              (workgroups of one agent, n_agent).  Each is its form's body (the .inc file) behind
+//                              swimmer_rollout_multi.inc, which points policy, deltas, mean, inv_std and the outputs
+//                              at the slices of agent blockIdx.y: per rollout the arithmetic of the
+//                              single-agent kernel without capture, hot loops pinned by the body's SW_PIN_LOOP with
+//                              pads of their own (*_multi_loop_pad below)
 //   swimmer_update.hip
 //   ars_update_kernel          sigma_R, policy step, V2 statistics merge; pure latency between
 //                              two rollout launches: one round of loads, then LDS only
+//   ars_update_multi_kernel    the same body (swimmer_update.inc) for many agents, grid (m*d + 1, n_agent)
 //   swimmer_cov.hip, swimmer_cov.h
 //   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound; its tile code
 //                              (swimmer_cov.h) also rides along in the segment-per-lane rollout launches (SideJob)
@@ -89,6 +98,31 @@ constexpr int row_loop_pad(int n, bool traj, bool mom)
 {
     if (n == 6 && !(traj && mom)) return traj ? 6 : 4;
     return n == 4 ? 5 : n == 5 ? 0 : n == 6 ? 5 : n == 7 ? 6 : 1;
+}
+#endif
+
+// The multi-agent kernels (ars_multi_*_kernel, sw_ars_rollouts_multi_f64) run their form's body behind another
+// prologue, so the same pad leaves their loops elsewhere in the line: they have pads of their own.
+//  * mirror-quad (n = 3, the form a batch of seeds runs in): SWEPT on the GPU over the eight pads that start the loop
+//    on an 8-byte boundary (1, 3, .. 15; profiles/r05_multi_pad_sweep.log, S = 1 and 64 agents, two passes).  At the
+//    pad that puts the V2 loop where its single-agent twin's sits (12: offset 28) the launch ran 205.0 us against the
+//    twin's 198.3; at every odd pad 197.9-199.1.  V1: 188.2-190.1, best at 3 and 11.  Pad 11 for both: 188.3 (twin
+//    188.6) and 198.2 (twin 198.3).
+//  * quad and row: NOT swept.  Each pad puts the hot loop at the offset its single-agent twin (the form's ARS kernel
+//    without capture, same n, same MOM) has in the same build -- scripts/multi_loop_offsets.py prints both -- where
+//    the loops hold the same instructions (row) or differ by one scalar move (quad).
+// -DSW_MULTI_LOOP_PAD=k overrides all of them for a sweep.
+#ifdef SW_MULTI_LOOP_PAD
+constexpr int oct_multi_loop_pad(bool) { return SW_MULTI_LOOP_PAD; }
+constexpr int quad_multi_loop_pad(bool) { return SW_MULTI_LOOP_PAD; }
+constexpr int row_multi_loop_pad(int, bool) { return SW_MULTI_LOOP_PAD; }
+#else
+constexpr int oct_multi_loop_pad(bool) { return 11; }
+constexpr int quad_multi_loop_pad(bool) { return 3; }
+constexpr int row_multi_loop_pad(int n, bool mom)
+{
+    return n == 4 ? (mom ? 1 : 3) : n == 5 ? (mom ? 11 : 15) : n == 6 ? (mom ? 11 : 13) : n == 7 ? (mom ? 10 : 1)
+                                                                                                 : (mom ? 9 : 4);
 }
 #endif
 
@@ -361,6 +395,27 @@ RolloutLauncher launch_oct3, launch_quad3, launch_row, launch_lane;
 using GateLauncher = int(const sw_params *sim, const RolloutPlan &plan, int64_t n_roll, int32_t H,
                          const RolloutArgs &a, double gate_thr, int32_t *admit, hipStream_t stream);
 GateLauncher launch_gate_oct3, launch_gate_quad3, launch_gate_row, launch_gate_lane;
+// The ARS rollouts of n_agent agents in one launch (sw_ars_rollouts_multi_f64).  Every array is the single-agent
+// array of sw_ars_rollouts_f64 once per agent, agent-major and dense: policy [n_agent][m][d], deltas
+// [n_agent][n_dir][m][d], mean / inv_std [n_agent][d] (both null: V1), returns / status [n_agent][2 n_dir],
+// moments [n_agent][ceil(2 n_dir / 16)][2d] (null: none).
+struct MultiArgs {
+    const double *policy, *deltas, *mean, *inv_std;
+    double *returns, *moments;
+    int32_t *status;
+};
+// Slots (rollouts a workgroup has lanes for) per workgroup of a form: the granule an agent's rollouts are padded to,
+// so that no workgroup -- and no 16-rollout moment row -- ever holds two agents.
+constexpr int form_slots(Form f) { return f == Form::Lane ? kRollBlock : kMomGroup; }
+// n_roll = 2 n_dir rollouts per agent; grid = (workgroups per agent, n_agent), blocks of plan.block threads.
+using MultiLauncher = int(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                          const MultiArgs &a, double nu, hipStream_t stream);
+MultiLauncher launch_multi_oct3, launch_multi_quad3, launch_multi_row, launch_multi_lane;
+inline dim3 multi_grid(const RolloutPlan &plan, int64_t n_agent, int64_t n_roll)
+{
+    const int per = form_slots(plan.form);
+    return dim3((unsigned)((n_roll + per - 1) / per), (unsigned)n_agent);
+}
 // Safe exploration (sw_safe_rollouts_f64); there is no safe quad kernel.
 using SafeLauncher = int(const sw_params *real, const sw_params *sim, const RolloutPlan &plan, int64_t n_roll,
                          int32_t H, const double *policies, int32_t cost_kind, int32_t cost_index, double sim_thresh,

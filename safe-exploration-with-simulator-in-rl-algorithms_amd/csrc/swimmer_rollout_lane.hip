@@ -44,6 +44,22 @@ ars_gate_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H, const
 #undef SW_GATE_BODY
 }
 
+// sw_ars_rollouts_multi_f64 in the lane form (any n, either model): the ARS rollouts of many agents in one launch,
+// the lane body behind the per-agent view (swimmer_rollout_multi.inc).  An agent's rollouts fill whole 64-lane
+// workgroups of their own; the lanes behind its last rollout idle.
+#define SW_MULTI_N N
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+ars_multi_lane_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H, sw_launch::MultiArgs all, double nu)
+{
+    constexpr bool ARS = true;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_N
+
 // ------------------------------------------------------------------------------------
 // Safe exploration (safe_ars/ars.py:101-153): every real step of a rollout is gated by a ONE-STEP look-ahead in a
 // simulator -- `isSafe` = sim_env.set_state(obs) + sim_env.step(action) + cost(sim obs) <= sim_thresh (:111-122,
@@ -191,6 +207,18 @@ int launch_gate_lane(const sw_params *sim, const RolloutPlan &plan, int64_t n_ro
                            stream, C, T, n_roll, H, a.policies, a.deltas, a.dir_begin, a.nu, a.mean, a.inv_std,
                            gate_thr, admit, a.returns, a.status);
     }, is_twin(sim));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_multi_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                      const MultiArgs &a, double nu, hipStream_t stream)
+{
+    const sw::Consts C = make_consts(p);
+    const sw::TwinConsts T = make_twin_consts(p);
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
+        hipLaunchKernelGGL((ars_multi_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
+                           dim3(plan.block), 0, stream, C, T, n_roll, H, a, nu);
+    }, is_twin(p));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 

@@ -1,5 +1,6 @@
-// Body of rollout_kernel (csrc/swimmer_rollout_lane.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
-// kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for token what it was) or 1 (the gate).
+// Body of rollout_kernel (csrc/swimmer_rollout_lane.hip), shared with its sw_ars_gate_f64 form and its multi-agent form
+// (sw_ars_rollouts_multi_f64): included INSIDE the kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for
+// token what it was; the multi-agent kernel behind swimmer_rollout_multi.inc) or 1 (the gate).
     constexpr int D = 2 * N + 2, M = N - 1;
     const int64_t r = (int64_t)blockIdx.x * kRollBlock + threadIdx.x;
     const bool active = r < n_roll;

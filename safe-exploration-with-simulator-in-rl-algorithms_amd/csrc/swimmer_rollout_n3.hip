@@ -78,6 +78,33 @@ ars_gate_oct3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__re
 }
 
 // ------------------------------------------------------------------------------------
+// sw_ars_rollouts_multi_f64 in the quad and the mirror-quad form: the ARS rollouts of many agents in one launch, the
+// form's body behind the per-agent view (swimmer_rollout_multi.inc).  No capture, no side job (kNoSide).
+#define SW_MULTI_N 3
+template <bool MOM>
+__global__ void __launch_bounds__(kRollBlock)
+ars_multi_quad3_kernel(sw::Consts C, int64_t n_roll, int32_t H, sw_launch::MultiArgs all, double nu, SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_quad3.inc"
+#undef SW_GATE_BODY
+}
+
+template <bool MOM>
+__global__ void __launch_bounds__(kOctBlock)
+ars_multi_oct3_kernel(sw::Consts C, int64_t n_roll, int32_t H, sw_launch::MultiArgs all, double nu, SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_oct3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_N
+
+// ------------------------------------------------------------------------------------
 // The safe-exploration gate (safe_rollout_kernel above has the semantics) for n = 3 in the MIRROR-QUAD form of
 // rollout_oct3_kernel: two quads of eight lanes per rollout, lane roles, reduced angles.  The geometry of a step
 // (sin / cos, cos(th_i - th_k), ...) depends on the angles only and is therefore SHARED by the simulator's look-ahead
@@ -280,6 +307,26 @@ int launch_gate_quad3(const sw_params *sim, const RolloutPlan &plan, int64_t n_r
                       double gate_thr, int32_t *admit, hipStream_t stream)
 {
     launch_gate_segment_per_lane(ars_gate_quad3_kernel, sim, plan, n_roll, H, a, gate_thr, admit, stream);
+    return launch_status();
+}
+
+int launch_multi_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                      const MultiArgs &a, double nu, hipStream_t stream)
+{
+    with_bools([&](auto MOM) {
+        hipLaunchKernelGGL(ars_multi_oct3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
+                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    }, a.moments != nullptr);
+    return launch_status();
+}
+
+int launch_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                       const MultiArgs &a, double nu, hipStream_t stream)
+{
+    with_bools([&](auto MOM) {
+        hipLaunchKernelGGL(ars_multi_quad3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
+                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    }, a.moments != nullptr);
     return launch_status();
 }
 

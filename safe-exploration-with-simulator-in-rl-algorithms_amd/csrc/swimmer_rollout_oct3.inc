@@ -1,5 +1,6 @@
-// Body of rollout_oct3_kernel (csrc/swimmer_rollout_n3.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
-// kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for token what it was) or 1 (the gate).
+// Body of rollout_oct3_kernel (csrc/swimmer_rollout_n3.hip), shared with its sw_ars_gate_f64 form and its multi-agent form
+// (sw_ars_rollouts_multi_f64): included INSIDE the kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for
+// token what it was; the multi-agent kernel behind swimmer_rollout_multi.inc) or 1 (the gate).
     side_flag(side);
     if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
         side_cov_tile<8, kOctBlock>(side);
@@ -109,7 +110,11 @@
     };
     // the geometry ping-pongs between G and Gn (no register copies): an even number of steps per trip
     int32_t t = 0;
+#ifdef SW_MULTI_N   // a multi-agent kernel: its own pad (swimmer_launch.h)
+    SW_PIN_LOOP(oct_multi_loop_pad(MOM));
+#else
     SW_PIN_LOOP(oct_loop_pad(TRAJ, MOM));
+#endif
 #if SW_OCT_UNROLL == 8
     // eight steps per trip: the loop's back edge costs a lone wave ~8-13 ns (2 / 4 / 8 steps per trip:
     // 0.2292 / 0.2272 / 0.2250 ms per launch, each at its best loop offset; profiles/r03_t, r03_w)

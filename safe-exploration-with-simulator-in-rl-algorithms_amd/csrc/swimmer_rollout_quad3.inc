@@ -1,5 +1,6 @@
-// Body of rollout_quad3_kernel (csrc/swimmer_rollout_n3.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
-// kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for token what it was) or 1 (the gate).
+// Body of rollout_quad3_kernel (csrc/swimmer_rollout_n3.hip), shared with its sw_ars_gate_f64 form and its multi-agent form
+// (sw_ars_rollouts_multi_f64): included INSIDE the kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for
+// token what it was; the multi-agent kernel behind swimmer_rollout_multi.inc) or 1 (the gate).
     side_flag(side);
     if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
         side_cov_tile<8, kRollBlock>(side);
@@ -137,7 +138,11 @@
     // four steps per trip, the geometry ping-pongs between G and Gn (no register copies)
     int32_t t = 0;
 #if SW_QUAD_UNROLL == 4
+#ifdef SW_MULTI_N   // a multi-agent kernel: its own pad (swimmer_launch.h)
+    SW_PIN_LOOP(quad_multi_loop_pad(MOM));
+#else
     SW_PIN_LOOP(SW_QUAD_LOOP_PAD);
+#endif
     for (; t + 4 <= H; t += 4) {
         one_step(G, Gn);
         one_step(Gn, G);

@@ -45,6 +45,21 @@ ars_gate_row_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__res
 #undef SW_GATE_BODY
 }
 
+// sw_ars_rollouts_multi_f64 in the row form, n = 4..8: the ARS rollouts of many agents in one launch, the row body
+// behind the per-agent view (swimmer_rollout_multi.inc).  No capture, no side job (kNoSide).
+#define SW_MULTI_N N
+template <int N, bool MOM>
+__global__ void __launch_bounds__(kRowBlock, (N <= 6 ? 2 : 1))
+ars_multi_row_kernel(sw::Consts C, int64_t n_roll, int32_t H, sw_launch::MultiArgs all, double nu, SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_row.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_N
+
 // ------------------------------------------------------------------------------------
 // The safe-exploration gate for n = 4..8 in the ROW form of rollout_row_kernel (one segment per lane, one rollout per
 // 16-lane DPP row): per env-step two `row_step`s -- the simulator's look-ahead on copies of the state with the
@@ -231,6 +246,16 @@ int launch_gate_row(const sw_params *sim, const RolloutPlan &plan, int64_t n_rol
     const bool known_n = with_n<4, 8>(sim->n, [&](auto N) {
         launch_gate_segment_per_lane(ars_gate_row_kernel<N.value>, sim, plan, n_roll, H, a, gate_thr, admit, stream);
     });
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_multi_row(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                     const MultiArgs &a, double nu, hipStream_t stream)
+{
+    const bool known_n = with_n<4, 8>(p->n, [&](auto N, auto MOM) {
+        hipLaunchKernelGGL((ars_multi_row_kernel<N.value, MOM.value>), multi_grid(plan, n_agent, n_roll),
+                           dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    }, a.moments != nullptr);
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 

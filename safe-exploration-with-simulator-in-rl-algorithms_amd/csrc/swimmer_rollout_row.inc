@@ -1,5 +1,6 @@
-// Body of rollout_row_kernel (csrc/swimmer_rollout_row.hip), shared with its sw_ars_gate_f64 form: included INSIDE the
-// kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for token what it was) or 1 (the gate).
+// Body of rollout_row_kernel (csrc/swimmer_rollout_row.hip), shared with its sw_ars_gate_f64 form and its multi-agent form
+// (sw_ars_rollouts_multi_f64): included INSIDE the kernels' braces with SW_GATE_BODY 0 (the rollout kernel, token for
+// token what it was; the multi-agent kernel behind swimmer_rollout_multi.inc) or 1 (the gate).
     side_flag(side);
     if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
         side_cov_tile<2 * N + 2, kRowBlock>(side);
@@ -110,7 +111,11 @@
         return __any((4.0 * C.h) * fabs(thd) > sw::kTripSlack);
     };
     int32_t t = 0;
+#ifdef SW_MULTI_N   // a multi-agent kernel: its own pad (swimmer_launch.h)
+    SW_PIN_LOOP(row_multi_loop_pad(N, MOM));
+#else
     SW_PIN_LOOP(row_loop_pad(N, TRAJ, MOM));
+#endif
     while (t < H) {   // two loops, not one loop with two bodies: merged, the compiler reconciles the bodies'
                       // register assignments with copies on the common path (profiles/r03_g_ab_range_check_variants.log)
         while (t < H) {                              // unchecked trips of (up to) four steps

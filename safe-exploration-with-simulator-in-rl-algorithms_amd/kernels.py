@@ -375,6 +375,75 @@ def ars_update(p: SwParams, returns, deltas, policy, alpha: float, b: float, top
     return policy
 
 
+def _want_i32(t, name, shape, device):
+    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise _lib.SwimmerHipError(f"{name}: expected int32 tensor of shape {tuple(shape)} on {device}")
+    return t
+
+
+def ars_rollouts_multi(p: SwParams, H: int, policy, deltas, nu: float, mean=None, inv_std=None, returns=None,
+                       moments=None, status=None):
+    """The exploration rollouts of S agents in ONE launch (sw_ars_rollouts_multi_f64): policy [S, m, d], deltas
+    [S, N, m, d], mean / inv_std [S, d] (both or neither).  Returns `returns` [S, 2N]: row a holds what
+    ars_rollouts gives for agent a's policy, deltas, mean and inv_std; moments ([S, moments_blocks(2N), 2d]) and
+    status (int32 [S, 2N]) are filled when given, agent by agent as ars_rollouts fills them."""
+    require_gpu()
+    if policy.dim() != 3 or policy.shape[0] < 1:
+        raise _lib.SwimmerHipError(f"policy: expected float64 tensor of shape (S, m, d), got {tuple(policy.shape)}")
+    S = policy.shape[0]
+    _want(policy, "policy", (S, p.m, p.d))
+    if deltas.dim() != 4 or deltas.shape[1] < 1:
+        raise _lib.SwimmerHipError(f"deltas: expected float64 tensor of shape (S, N, m, d), got {tuple(deltas.shape)}")
+    N = deltas.shape[1]
+    _want(deltas, "deltas", (S, N, p.m, p.d))
+    dev = policy.device
+    if (mean is None) != (inv_std is None):
+        raise _lib.SwimmerHipError("mean and inv_std must be given together")
+    if mean is not None:
+        _want(mean, "mean", (S, p.d))
+        _want(inv_std, "inv_std", (S, p.d))
+    if moments is not None:
+        _want(moments, "moments", (S, moments_blocks(2 * N), 2 * p.d))
+    if status is not None:
+        _want_i32(status, "status", (S, 2 * N), dev)
+    returns = _f64((S, 2 * N), dev) if returns is None else _want(returns, "returns", (S, 2 * N))
+    check(load().sw_ars_rollouts_multi_f64(ctypes.byref(p), S, N, H, ptr(policy), ptr(deltas), float(nu), ptr(mean),
+                                           ptr(inv_std), ptr(returns), ptr(moments), ptr(status), stream_ptr()),
+          "sw_ars_rollouts_multi_f64")
+    return returns
+
+
+def ars_update_multi(p: SwParams, returns, deltas, policy, alpha: float, b: float, top_b: int = 0,
+                     moments=None, running=None, n_new_states: int = 0, mean=None, inv_std=None,
+                     sigma_out=None):
+    """ars_update for S agents in ONE launch (sw_ars_update_multi_f64), in place: returns [S, 2N], deltas
+    [S, N, m, d], policy [S, m, d]; with `running` ([S, 1 + 2d]) also moments [S, rows, 2d], mean and inv_std
+    [S, d]; sigma_out [S] or None."""
+    require_gpu()
+    if returns.dim() != 2 or returns.shape[0] < 1 or returns.shape[1] < 2 or returns.shape[1] % 2:
+        raise _lib.SwimmerHipError(f"returns: expected float64 tensor of shape (S, 2N), got {tuple(returns.shape)}")
+    S, n_dir = returns.shape[0], returns.shape[1] // 2
+    _want(returns, "returns", (S, 2 * n_dir))
+    _want(policy, "policy", (S, p.m, p.d))
+    _want(deltas, "deltas", (S, n_dir, p.m, p.d))
+    n_rows = 0
+    if running is not None:
+        _want(running, "running", (S, 1 + 2 * p.d))
+        _want(mean, "mean", (S, p.d))
+        _want(inv_std, "inv_std", (S, p.d))
+        if moments is None or moments.dim() != 3:
+            raise _lib.SwimmerHipError("moments: expected float64 tensor of shape (S, rows, 2d) next to running")
+        n_rows = moments.shape[1]
+        _want(moments, "moments", (S, n_rows, 2 * p.d))
+    if sigma_out is not None:
+        _want(sigma_out, "sigma_out", (S,))
+    check(load().sw_ars_update_multi_f64(ctypes.byref(p), S, n_dir, ptr(returns), ptr(deltas), ptr(policy),
+                                         float(alpha), float(b), int(top_b), ptr(moments), n_rows, ptr(running),
+                                         int(n_new_states), ptr(mean), ptr(inv_std), ptr(sigma_out), stream_ptr()),
+          "sw_ars_update_multi_f64")
+    return policy
+
+
 def ars_update_gathered(p: SwParams, n_dir: int, gathered, world: int, chunk: int, rows_chunk: int,
                         deltas, policy, alpha: float, b: float, top_b: int = 0, running=None,
                         n_new_states: int = 0, mean=None, inv_std=None, sigma_out=None):

@@ -1,0 +1,183 @@
+"""sw_ars_rollouts_multi_f64 / sw_ars_update_multi_f64 against their single-agent entry points, agent by agent and
+bit for bit.  Every agent has its own policy, deltas and (V2) statistics, so a kernel that reads another agent's
+data, mixes agents in a moment row or lets a padding slot count cannot pass."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:      # the quad-form child below runs this file as a script
+    sys.path.insert(0, ROOT)
+
+import swimmer_amd as sw  # noqa: E402
+from swimmer_amd import kernels  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+H = 60
+NU = 0.05
+
+
+def _agent_inputs(n, N, S, v2, seed=0):
+    """Per agent: a random policy in (-1, 1), its own deltas and, for V2, its own mean in (-0.1, 0.1) and inv_std in
+    (0.5, 2) -- the ranges of _gate_inputs in tests/test_safe_ars_agent_gpu.py."""
+    m, d = n - 1, 2 * n + 2
+    rng = np.random.RandomState(100000 * seed + 1000 * n + 10 * N + S)
+    policy = torch.tensor(rng.uniform(-1, 1, (S, m, d)), device=DEV)
+    deltas = torch.tensor(2 * rng.rand(S, N, m, d) - 1, device=DEV)
+    mean = inv_std = None
+    if v2:
+        mean = torch.tensor(rng.uniform(-0.1, 0.1, (S, d)), device=DEV)
+        inv_std = torch.tensor(rng.uniform(0.5, 2.0, (S, d)), device=DEV)
+    return policy, deltas, mean, inv_std
+
+
+def _compare_rollouts(p, n, N, S, v2):
+    """Multi launch (outputs poisoned first) against one ars_rollouts call per agent; returns the number of agents."""
+    policy, deltas, mean, inv_std = _agent_inputs(n, N, S, v2)
+    rows = kernels.moments_blocks(2 * N)
+    returns = torch.full((S, 2 * N), float("nan"), dtype=torch.float64, device=DEV)
+    moments = torch.full((S, rows, 2 * p.d), float("nan"), dtype=torch.float64, device=DEV)
+    status = torch.full((S, 2 * N), -1, dtype=torch.int32, device=DEV)
+    out = kernels.ars_rollouts_multi(p, H, policy, deltas, NU, mean, inv_std, returns=returns, moments=moments,
+                                     status=status)
+    assert out is returns
+    R, M, St = returns.cpu().numpy(), moments.cpu().numpy(), status.cpu().numpy()
+    assert not np.isnan(R).any() and not np.isnan(M).any(), "an output cell was left unwritten"
+    assert (St == 0).all()
+    for a in range(S):
+        mom1 = torch.zeros((rows, 2 * p.d), dtype=torch.float64, device=DEV)
+        st1 = torch.full((2 * N,), -1, dtype=torch.int32, device=DEV)
+        r1 = kernels.ars_rollouts(p, H, policy[a], deltas[a], NU, 0, N, None if mean is None else mean[a],
+                                  None if inv_std is None else inv_std[a], moments=mom1, status=st1)
+        assert (st1.cpu().numpy() == 0).all()
+        assert np.array_equal(R[a], r1.cpu().numpy()), (a, "returns")
+        assert np.array_equal(M[a], mom1.cpu().numpy()), (a, "moment rows")
+    return S
+
+
+@pytest.mark.parametrize("v2", [False, True], ids=["V1", "V2"])
+@pytest.mark.parametrize("form", ["auto", "lane"])
+@pytest.mark.parametrize("S", [1, 3, 9])
+@pytest.mark.parametrize("N", [1, 7, 8, 9])      # 2N = 2, 14, 16, 18: below, just below, exactly, across a moment row
+@pytest.mark.parametrize("n", [2, 3, 6])         # lane only, mirror-quad, row
+def test_multi_rollouts_equal_single_agent_launches(n, N, S, form, v2):
+    # auto: S * 16 * ceil(2N / 16) <= 288 slots, far below 8192 -- the batch and the single launches take the same form
+    p = sw.SwParams.make(n, 0.8, 1.2, 10.2, 1e-3, flags=sw._lib.kernel_flags(form))
+    _compare_rollouts(p, n, N, S, v2)
+
+
+def test_multi_rollouts_without_moments_and_status():
+    """The optional outputs left out: V1 agents as ARSAgentBatch launches them."""
+    p = sw.SwParams.make(3)
+    policy, deltas, _, _ = _agent_inputs(3, 9, 3, False)
+    R = kernels.ars_rollouts_multi(p, H, policy, deltas, NU).cpu().numpy()
+    for a in range(3):
+        assert np.array_equal(R[a], kernels.ars_rollouts(p, H, policy[a], deltas[a], NU, 0, 9).cpu().numpy())
+
+
+def test_quad3_multi_form_in_a_child_process():
+    """SWIMMER_N3_KERNEL=quad (read once per process) sends n = 3 to the quad form: batch and single launches alike."""
+    env = dict(os.environ, SWIMMER_N3_KERNEL="quad")
+    done = subprocess.run([sys.executable, os.path.abspath(__file__), "quad-child"], env=env, capture_output=True,
+                          text=True, timeout=300)
+    assert done.returncode == 0, done.stdout + done.stderr
+    assert "quad-child ok" in done.stdout
+
+
+def _update_inputs(rng, S, N, d, m, rows, count):
+    returns = torch.tensor(rng.uniform(-3, 3, (S, 2 * N)), device=DEV)
+    deltas = torch.tensor(2 * rng.rand(S, N, m, d) - 1, device=DEV)
+    x = rng.normal(0.0, 1.0, (S, rows, count, d)) * rng.uniform(0.5, 2.0, (S, 1, 1, d))
+    moments = torch.tensor(np.concatenate([x.sum(axis=2), (x * x).sum(axis=2)], axis=2), device=DEV)
+    return returns, deltas, moments
+
+
+@pytest.mark.parametrize("v2", [False, True], ids=["V1", "V2"])
+@pytest.mark.parametrize("top_b", [0, 4])
+@pytest.mark.parametrize("N", [1, 9, 300])
+def test_multi_update_equals_single_agent_updates(N, top_b, v2):
+    n, S, count = 3, 3, 40
+    p = sw.SwParams.make(n)
+    m, d = p.m, p.d
+    rows = kernels.moments_blocks(2 * N)
+    rng = np.random.RandomState(7 * N + top_b)
+    f64 = dict(dtype=torch.float64, device=DEV)
+    policy = torch.tensor(rng.uniform(-1, 1, (S, m, d)), device=DEV)
+    running = torch.zeros((S, 1 + 2 * d), **f64) if v2 else None
+    mean = torch.zeros((S, d), **f64) if v2 else None
+    inv_std = torch.ones((S, d), **f64) if v2 else None
+    sigma = torch.zeros(S, **f64)
+    # the single-agent state, agent by agent
+    one = [dict(policy=policy[a].clone(), running=None if not v2 else running[a].clone(),
+                mean=None if not v2 else mean[a].clone(), inv_std=None if not v2 else inv_std[a].clone(),
+                sigma=torch.zeros(1, **f64)) for a in range(S)]
+    n_new = rows * count
+    for call in range(2):       # the second call merges into running statistics that are no longer zero
+        returns, deltas, moments = _update_inputs(rng, S, N, d, m, rows, count)
+        kernels.ars_update_multi(p, returns, deltas, policy, 0.02, float(N), top_b, moments=moments if v2 else None,
+                                 running=running, n_new_states=n_new, mean=mean, inv_std=inv_std, sigma_out=sigma)
+        for a, o in enumerate(one):
+            kernels.ars_update(p, returns[a], deltas[a], o["policy"], 0.02, float(N), top_b,
+                               moments=moments[a] if v2 else None, running=o["running"], n_new_states=n_new,
+                               mean=o["mean"], inv_std=o["inv_std"], sigma_out=o["sigma"])
+            assert np.array_equal(policy[a].cpu().numpy(), o["policy"].cpu().numpy()), (call, a, "policy")
+            assert np.array_equal(sigma[a:a + 1].cpu().numpy(), o["sigma"].cpu().numpy()), (call, a, "sigma")
+            if v2:
+                for name, t in (("running", running), ("mean", mean), ("inv_std", inv_std)):
+                    assert np.array_equal(t[a].cpu().numpy(), o[name].cpu().numpy()), (call, a, name)
+    assert np.isfinite(policy.cpu().numpy()).all()
+    if v2:
+        assert (running[:, 0].cpu().numpy() == 2 * n_new).all()
+
+
+def test_argument_errors_leave_the_outputs_alone():
+    p = sw.SwParams.make(3)
+    S, N = 2, 3
+    policy, deltas, mean, inv_std = _agent_inputs(3, N, S, True)
+    returns = torch.full((S, 2 * N), 7.0, dtype=torch.float64, device=DEV)
+    status = torch.full((S, 2 * N), -1, dtype=torch.int32, device=DEV)
+    lib, ptr, ok = sw._lib.load(), sw._lib.ptr, ctypes.byref(p)
+
+    def roll(S_=S, N_=N, pol=policy, dl=deltas, mn=mean, isd=inv_std, ret=returns, params=ok):
+        return lib.sw_ars_rollouts_multi_f64(params, S_, N_, H, ptr(pol), ptr(dl), NU, ptr(mn), ptr(isd), ptr(ret),
+                                             None, ptr(status), None)
+    assert roll(S_=0) == 3                     # SW_ERR_SIZE
+    assert roll(N_=0) == 3
+    assert roll(pol=None) == 1                 # SW_ERR_NULL
+    assert roll(dl=None) == 1
+    assert roll(ret=None) == 1
+    assert roll(isd=None) == 1                 # mean without inv_std
+    assert roll(mn=None) == 1
+    assert roll(params=None) == 1
+    assert roll(params=ctypes.byref(sw.SwParams.make(9))) == 2
+    upd = lib.sw_ars_update_multi_f64
+    before = policy.clone()
+    assert upd(ok, 0, N, ptr(returns), ptr(deltas), ptr(policy), 0.01, 1.0, 0, None, 0, None, 0, None, None, None,
+               None) == 3
+    assert upd(ok, S, 0, ptr(returns), ptr(deltas), ptr(policy), 0.01, 1.0, 0, None, 0, None, 0, None, None, None,
+               None) == 3
+    assert upd(ok, S, N, None, ptr(deltas), ptr(policy), 0.01, 1.0, 0, None, 0, None, 0, None, None, None,
+               None) == 1
+    torch.cuda.synchronize()
+    assert (returns.cpu().numpy() == 7.0).all() and (status.cpu().numpy() == -1).all()
+    assert np.array_equal(policy.cpu().numpy(), before.cpu().numpy())
+    with pytest.raises(sw.SwimmerHipError):
+        kernels.ars_rollouts_multi(p, H, policy, deltas, NU, mean, None)
+    with pytest.raises(sw.SwimmerHipError):
+        kernels.ars_rollouts_multi(p, H, policy, deltas[:1], NU)
+    with pytest.raises(sw.SwimmerHipError):
+        kernels.ars_update_multi(p, returns, deltas[:, :2], policy, 0.01, 1.0)
+
+
+if __name__ == "__main__" and sys.argv[1:] == ["quad-child"]:
+    # the child of test_quad3_multi_form_in_a_child_process: 2N = 18 crosses a moment row, V1 and V2
+    for v2_ in (False, True):
+        _compare_rollouts(sw.SwParams.make(3, 0.8, 1.2, 10.2, 1e-3), 3, 9, 3, v2_)
+    print("quad-child ok")
