@@ -33,6 +33,8 @@
  *                        Estimator.estimate_real_env_param's search)  ars/estimator.py:36-62, :89-110
  *   sw_safe_rollouts_f64 Safe_ARS.isSafe + Safe_ARS.rollout (the one-step simulator look-ahead that gates
  *                        every real step)                            safe_ars/ars.py:111-153
+ *   sw_cacla_run_f64     CACLA_agent.run with TwoLayersNet / ActorFA / CriticFA, for every agent of the
+ *                        hyper-parameter grid at once   cacla/cacla_agent.py:19-58, :135-199, cacla/swimmer_experiment.py:21-57
  *
  * Layouts (d = 2n+2 observation size, m = n-1 action size):
  *   state, SoA    [d][n_env]   field-major: row f holds field f of every env; fields are
@@ -278,6 +280,37 @@ int sw_ars_update_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, 
                             int64_t top_b, const double *moments, int64_t n_moment_rows,
                             double *running, int64_t n_new_states, double *mean, double *inv_std,
                             double *sigma_out, void *stream);
+
+/* ---- CACLA (cacla/cacla_agent.py): whole training runs of many independent agents in ONE launch ----
+ * An agent is n networks -- the n - 1 actors of ActorFA (one per torque), then the critic of CriticFA -- each a
+ * TwoLayersNet(d, SW_CACLA_HIDDEN): linear1 (d -> 12), relu, linear2 (12 -> 1), fp64.  One network is
+ * SW_CACLA_NET_DOUBLES(n) doubles:
+ *   W1 [12][d] row-major (linear1.weight) | b1 [12] (linear1.bias) | W2 [12] (linear2.weight) | b2 (linear2.bias)
+ * sw_cacla_run_f64 runs n_iter steps of CACLA_agent.run (cacla_agent.py:170-193) for n_agent agents, one wave each:
+ *   train != 0: FA_act = actors(state); action = FA_act + noise[t]; new_state, reward = step(action);
+ *               temp_diff = reward + gamma V(new_state) - V(state); critic += alpha temp_diff dV/dw at `state`;
+ *               if temp_diff > 0: actor_i += alpha (action_i - FA_act_i) dA_i/dw at `state`; state = new_state
+ *   train == 0: the reference as written (:173-178): no updates, and the actors see the state THE CALL STARTED
+ *               FROM at every step while the swimmer keeps stepping (so a split run is not one run); weights are
+ *               not written
+ * No action clipping, no reset, `done` ignored.  Arithmetic is not trapped: NaN propagates into the rewards (the
+ * reference takes np.nanmean over seeds) and a NaN temp_diff skips the actor update.
+ *   gamma, alpha  : [n_agent]
+ *   noise         : [n_agent][n_iter][n-1], added to the actors' outputs: the caller's N(0, sigma) draws
+ *   weights       : in/out [n_agent][n][SW_CACLA_NET_DOUBLES(n)]
+ *   state         : in/out [n_agent][d], AoS: one agent's observation is contiguous; out = the swimmer's state
+ *   rewards       : [n_agent][n_iter]
+ *   actor_updates : NULL or [n_agent], += the steps with temp_diff > 0
+ *   status        : NULL or [n_agent], |= SW_STATUS_SINGULAR / NONFINITE (state after the call) / RANGE; zero it
+ *                   before the first call of a run
+ * weights and state are in/out so that a run can be split into launches: the split changes no bit (train != 0).
+ * Errors, before any HIP call: NULL pointer SW_ERR_NULL; n_agent < 1, n_agent > 2^31 - 1 or n_iter < 0 SW_ERR_SIZE;
+ * twin model SW_ERR_PARAM; n outside 2..8 SW_ERR_SEGMENTS.  n_iter = 0 writes nothing. */
+#define SW_CACLA_HIDDEN 12 /* cacla_agent.py:165-166 */
+#define SW_CACLA_NET_DOUBLES(n) (SW_CACLA_HIDDEN * (2 * (n) + 2) + 2 * SW_CACLA_HIDDEN + 1)
+int sw_cacla_run_f64(const sw_params *p, int64_t n_agent, int32_t n_iter, int32_t train,
+                     const double *gamma, const double *alpha, const double *noise, double *weights,
+                     double *state, double *rewards, int32_t *actor_updates, int32_t *status, void *stream);
 
 /* The same update reading an all-gathered buffer in place (no repacking between the
  * collective and the update):  gathered = `world` segments of

@@ -7,6 +7,8 @@ Public surface (mirrors the reference's module layout for this path):
     ars.Experiment                            ars/experiment.py  (its seeds train as one ars.ARSAgentBatch)
     ars.EnvParam / ars.ARSParam               ars/parameters.py
     safe_ars.Basic_ARS / safe_ars.Safe_ARS    safe_ars/ars.py  (batched one-step consumers of the step kernel)
+    cacla.CACLA_agent / cacla.CACLABatch      cacla/cacla_agent.py  (whole training runs in one fused launch)
+    cacla.swimmer_experiment                  cacla/swimmer_experiment.py  (the whole grid as one batch)
     kernels.*                                 thin wrappers of the C ABI (include/swimmer_hip.h)
 """
 from . import _build, _lib, kernels  # noqa: F401
@@ -14,6 +16,7 @@ from ._lib import SwParams, SwimmerHipError  # noqa: F401
 from .envs import SwimmerEnv, VecSwimmerEnv  # noqa: F401
 from .ars import ARSAgent, ARSAgentBatch, ARSParam, EnvParam, Environment, Experiment  # noqa: F401
 from . import safe_ars  # noqa: F401
+from . import cacla  # noqa: F401
 
 __all__ = ["SwParams", "SwimmerHipError", "SwimmerEnv", "VecSwimmerEnv", "ARSAgent", "ARSAgentBatch", "ARSParam",
            "EnvParam", "Environment", "Experiment", "kernels"]

@@ -1,0 +1,79 @@
+"""CACLA on the swimmer over a grid of hyper-parameters: the reference's cacla/swimmer_experiment.py:21-57 without
+Ray.  Where the reference starts one Ray task per (gamma, alpha, sigma) and trains that task's seeds one after the
+other, the whole grid -- every setting times every seed -- is ONE CACLABatch: one launch per chunk of steps.
+
+Seeds: the reference seeds nothing (each Ray worker starts from its own entropy); here the agents of a setting are
+seeded 0 .. n_seed - 1, so a curve can be reproduced, and grid() gives for a setting what experience() gives.
+
+Files, under out_dir (created when missing; the reference's "results/cacla/"): `<stem>.npy` with the setting's
+rewards [n_seed, n_iter] and -- when matplotlib imports -- `<stem>.png`, the reference's figure (:36-44), with
+<stem> = gamma=<round(gamma, 3)>_alpha=<alpha>_sigma=<sigma> as there.
+"""
+import os
+
+import numpy as np
+
+from .cacla_agent import CACLABatch
+
+
+def stem(gamma, alpha, sigma):
+    return f"gamma={round(float(gamma), 3)}_alpha={alpha}_sigma={sigma}"
+
+
+def _curve(rewards):
+    """mean and std over the seeds as the reference takes them (:31-32): a diverged seed's NaN is left out."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)    # a step at which every seed is NaN
+        return np.nanmean(rewards, axis=0), np.nanstd(rewards, axis=0)
+
+
+def _figure(env, gamma, alpha, sigma, H, mean, std, path):
+    try:
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+    except ImportError:
+        return
+    n_iter = len(mean)
+    t = np.linspace(0, n_iter, n_iter)
+    fig = Figure()
+    FigureCanvasAgg(fig)
+    axes = fig.add_subplot(111)
+    axes.plot(t, mean, color="#CC4F1B", label=f"gamma={round(float(gamma), 3)}, alpha={alpha}, sigma={sigma}")
+    axes.fill_between(t, mean - std, mean + std, alpha=0.5, edgecolor="#CC4F1B", facecolor="#FF9848")
+    axes.legend()
+    axes.set_xlabel("Timesteps")
+    axes.set_ylabel(f"Sum of last {H} rewards")
+    axes.set_title(f"CACLA on {env.envName} learning curve")
+    fig.savefig(path)
+
+
+def grid(env, gammas, alphas, sigmas, n_iter, n_seed=3, out_dir="results/cacla/", H=1000, chunk=2048):
+    """Every (gamma, alpha, sigma) of the three lists (gamma slowest, as the reference's loop, :55) with n_seed
+    agents each, trained together.  Returns {(gamma, alpha, sigma): (mean [n_iter], std [n_iter])}; out_dir None
+    writes no files."""
+    settings = [(g, a, s) for g in gammas for a in alphas for s in sigmas]
+    if not settings or n_seed < 1:
+        raise ValueError("grid needs at least one setting and one seed")
+    per_agent = [st for st in settings for _ in range(n_seed)]
+    batch = CACLABatch(env, [st[0] for st in per_agent], [st[1] for st in per_agent], [st[2] for st in per_agent],
+                       list(range(n_seed)) * len(settings))
+    rewards = batch.run(n_iter, chunk=chunk).reshape(len(settings), n_seed, n_iter)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    curves = {}
+    for (g, a, s), r in zip(settings, rewards):
+        mean, std = _curve(r)
+        curves[(g, a, s)] = (mean, std)
+        print(f"Last mean reward obtained for gamma={round(float(g), 3)}, alpha={a}, sigma={s}: "
+              f"{mean[-1] if n_iter else float('nan')}")
+        if out_dir is not None:
+            np.save(os.path.join(out_dir, stem(g, a, s)), r)
+            _figure(env, g, a, s, H, mean, std, os.path.join(out_dir, stem(g, a, s) + ".png"))
+    return curves
+
+
+def experience(env, gamma, alpha, sigma, n_iter, H=1000, n_seed=3, out_dir="results/cacla/"):
+    """One setting of the grid (swimmer_experiment.py:21-44): (t, mean, std) of its n_seed agents."""
+    mean, std = grid(env, [gamma], [alpha], [sigma], n_iter, n_seed=n_seed, out_dir=out_dir, H=H)[(gamma, alpha, sigma)]
+    return np.linspace(0, n_iter, n_iter), mean, std

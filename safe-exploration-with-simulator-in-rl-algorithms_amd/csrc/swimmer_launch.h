@@ -44,6 +44,12 @@
 //   swimmer_cov.hip, swimmer_cov.h
 //   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound; its tile code
 //                              (swimmer_cov.h) also rides along in the segment-per-lane rollout launches (SideJob)
+//   swimmer_cacla.hip (a translation unit of its own)
+//   cacla_kernel<N,TRAIN>      sw_cacla_run_f64: CACLA training runs of many independent agents, n_iter sequential
+//                              steps in one launch, ONE WAVE PER AGENT: the agent's n two-layer networks in registers
+//                              (a hidden unit per lane, two from n = 6), the physics redundantly in every lane, the
+//                              n + 1 network outputs of a step summed through LDS in a fixed order and handed out
+//                              with v_readlane; instruction-issue bound like the latency forms
 //   swimmer_abi.hip
 //   the rollout entry points and the native ARS iteration pipeline (sw_ars_pipeline_*: copy stream, progress
 //   flag, 4-slot buffer ring; the covariance pass rides along in the next rollout launch)

@@ -444,6 +444,40 @@ def ars_update_multi(p: SwParams, returns, deltas, policy, alpha: float, b: floa
     return policy
 
 
+CACLA_HIDDEN = 12   # SW_CACLA_HIDDEN: the reference's hidden width (cacla_agent.py:165-166)
+
+
+def cacla_net_doubles(n: int) -> int:
+    """SW_CACLA_NET_DOUBLES(n): one TwoLayersNet(d = 2n + 2, 12) as W1 [12][d] | b1 [12] | W2 [12] | b2."""
+    return CACLA_HIDDEN * (2 * n + 2) + 2 * CACLA_HIDDEN + 1
+
+
+def cacla_run(p: SwParams, n_iter: int, train: bool, gamma, alpha, noise, weights, state, rewards=None,
+              actor_updates=None, status=None):
+    """n_iter CACLA steps of A independent agents in ONE launch (sw_cacla_run_f64), one wave per agent: gamma, alpha
+    [A], noise [A, n_iter, m] (added to the actors' outputs), weights [A, n, cacla_net_doubles(n)] and state [A, d]
+    updated in place (weights only when training), actor_updates / status int32 [A] accumulated when given.
+    Returns `rewards` [A, n_iter]."""
+    require_gpu()
+    if gamma.dim() != 1 or gamma.shape[0] < 1:
+        raise _lib.SwimmerHipError(f"gamma: expected float64 tensor of shape (A,), got {tuple(gamma.shape)}")
+    A, dev = gamma.shape[0], gamma.device
+    _want(gamma, "gamma", (A,))
+    _want(alpha, "alpha", (A,))
+    _want(noise, "noise", (A, n_iter, p.m))
+    _want(weights, "weights", (A, p.n, cacla_net_doubles(p.n)))
+    _want(state, "state", (A, p.d))
+    if actor_updates is not None:
+        _want_i32(actor_updates, "actor_updates", (A,), dev)
+    if status is not None:
+        _want_i32(status, "status", (A,), dev)
+    rewards = _f64((A, n_iter), dev) if rewards is None else _want(rewards, "rewards", (A, n_iter))
+    check(load().sw_cacla_run_f64(ctypes.byref(p), A, int(n_iter), 1 if train else 0, ptr(gamma), ptr(alpha),
+                                  ptr(noise), ptr(weights), ptr(state), ptr(rewards), ptr(actor_updates),
+                                  ptr(status), stream_ptr()), "sw_cacla_run_f64")
+    return rewards
+
+
 def ars_update_gathered(p: SwParams, n_dir: int, gathered, world: int, chunk: int, rows_chunk: int,
                         deltas, policy, alpha: float, b: float, top_b: int = 0, running=None,
                         n_new_states: int = 0, mean=None, inv_std=None, sigma_out=None):
