@@ -88,6 +88,12 @@ extern "C" {
 #define SW_FLAG_ROLLOUT_QUAD 2 /* one segment per lane (latency form): a DPP quad per rollout for
                                   n = 3, a 16-lane DPP row per rollout for n = 4..8; n = 2 ignores it */
 
+/* sw_params.flags: n = 3 rollouts with trajectory capture AND V2 moments record a step with one wave-wide store and
+ * one moment pair (all eight state components of a rollout on its eight lanes).  This bit keeps them on the kernel
+ * that records with three partly masked stores and six sums instead.  Same outputs bit for bit; for A/B measurements
+ * and for tests.  Launches without capture or without moments ignore it. */
+#define SW_FLAG_CAPTURE_SPLIT 8
+
 /* sw_params.flags: which of the reference's two swimmer models the kernels integrate.
  * Default (bit clear): the Gym env (envs/gym_swimmer/swimmer/remy_swimmer_env.py, explicit
  * Euler, reset = (0, 0, pi/2, 0, ...)).  Bit set: the native RL-Glue environment

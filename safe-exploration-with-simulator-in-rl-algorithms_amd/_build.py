@@ -20,8 +20,8 @@ HOST_ONLY = {"host_rng.cpp"}   # plain C++, no device pass: it picks its vector 
                                # run time (x86 builtins the device pass of a HIP compile refuses)
 HEADERS = ["rlglue_env.cpp", os.path.join("..", "..", "include", "rlglue_swimmer.h"),
            "swimmer_launch.h", "swimmer_cov.h", "swimmer_device.h", "swimmer_rollout_lane.inc",
-           "swimmer_rollout_quad3.inc", "swimmer_rollout_oct3.inc", "swimmer_rollout_row.inc",
-           "swimmer_rollout_multi.inc", "swimmer_update.inc", "swimmer_quad3.h",
+           "swimmer_rollout_quad3.inc", "swimmer_rollout_oct3.inc", "swimmer_rollout_octp3.inc",
+           "swimmer_rollout_row.inc", "swimmer_rollout_multi.inc", "swimmer_update.inc", "swimmer_quad3.h",
            "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h",
            os.path.join("..", "..", "include", "swimmer_hip.h")] + FAMILIES
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + os.environ.get("SWIMMER_HIPCC_EXTRA", "").split()

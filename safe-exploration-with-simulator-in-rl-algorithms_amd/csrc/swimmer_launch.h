@@ -21,6 +21,9 @@
 //                              mirror quads per rollout (sine / cosine, Gdot_x / Gdot_y;
 //                              swimmer_oct3.h): the latency form, instruction-issue bound; up to
 //                              8192 rollouts (one wave per SIMD)
+//   rollout_octp3_kernel       the same with capture AND V2 moments in the packed record form: one trajectory store
+//                              and one moment pair per step (swimmer_rollout_octp3.inc); bit-identical outputs;
+//                              SW_FLAG_CAPTURE_SPLIT keeps such a launch on rollout_oct3_kernel<.., true, true>
 //   rollout_quad3_kernel       n = 3, one DPP quad per rollout (swimmer_quad3.h): 8193 .. 16384 rollouts
 //   swimmer_rollout_row.hip
 //   rollout_row_kernel<N>      n = 4..8, one segment per lane, one rollout per 16-lane DPP row
@@ -92,6 +95,14 @@ constexpr int oct_loop_pad(bool, bool) { return SW_OCT_LOOP_PAD; }
 #else
 constexpr int oct_loop_pad(bool traj, bool mom) { return traj ? (mom ? 5 : 6) : (mom ? 6 : 2); }
 #endif
+// the packed-record form of the mirror-quad kernel (rollout_octp3_kernel): other code between pin and loop, a pad of
+// its own.  Swept over all sixteen 4-byte offsets (profiles/r06_b_octp_pad_sweep.log, two passes): the even pads, which
+// start the loop on an 8-byte boundary, ran 0.2164-0.2182 ms per launch, the odd ones 0.2176-0.2204; 2, 4 and 6 are
+// the best three (0.2164-0.2167), 4 is pinned.  -DSW_OCTP_LOOP_PAD=k overrides it for a sweep
+#ifndef SW_OCTP_LOOP_PAD
+#define SW_OCTP_LOOP_PAD 4
+#endif
+constexpr int oct_packed_loop_pad() { return SW_OCTP_LOOP_PAD; }
 #ifndef SW_QUAD_LOOP_PAD
 #define SW_QUAD_LOOP_PAD 0
 #endif
@@ -188,7 +199,7 @@ int validate_params(const sw_params *p)
 {
     if (!p) return SW_ERR_NULL;
     if (p->n < 2 || p->n > SW_MAX_SEGMENTS) return SW_ERR_SEGMENTS;
-    if (p->flags & ~(SW_FLAG_ROLLOUT_LANE | SW_FLAG_ROLLOUT_QUAD | SW_FLAG_MODEL_TWIN)) return SW_ERR_PARAM;
+    if (p->flags & ~(SW_FLAG_ROLLOUT_LANE | SW_FLAG_ROLLOUT_QUAD | SW_FLAG_MODEL_TWIN | SW_FLAG_CAPTURE_SPLIT)) return SW_ERR_PARAM;
     if (!(p->l_i > 0.0) || !(p->m_i > 0.0) || !isfinite(p->l_i) || !isfinite(p->m_i) ||
         !isfinite(p->k) || !isfinite(p->h) || !isfinite(p->dir_x) || !isfinite(p->dir_y))
         return SW_ERR_PARAM;

@@ -284,4 +284,17 @@ __device__ __forceinline__ double oct3_dynamics(const Consts &C, const OctLane &
     return det;
 }
 
+// The packed record of rollout_octp3_kernel (swimmer_rollout_octp3.inc): one value per lane of the rollout.
+// Quad A's segment lanes keep `th`; the B lanes (banks 2 and 3 of the 16-lane row) take QUAD A's thd through
+// row_ror:8 -- two v_mov_b32_dpp that leave the A lanes' halves untouched; lane 3 of either quad takes its own Pu.
+// A select, not 0/1-weighted FMAs: NaN and inf pass through exactly as the three-store form records them.
+__device__ __forceinline__ double octp3_pack(double th, double thd, double Pu, bool lane3)
+{
+    int lo = __double2loint(th), hi = __double2hiint(th);
+    lo = __builtin_amdgcn_update_dpp(lo, __double2loint(thd), kDppRowRor8, 0xf, 0xc, false);
+    hi = __builtin_amdgcn_update_dpp(hi, __double2hiint(thd), kDppRowRor8, 0xf, 0xc, false);
+    const double Z = __hiloint2double(hi, lo);
+    return lane3 ? Pu : Z;
+}
+
 }  // namespace sw

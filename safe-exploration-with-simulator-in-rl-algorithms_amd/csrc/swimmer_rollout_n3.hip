@@ -1,6 +1,6 @@
 // swimmer_rollout_n3.hip -- n = 3 rollouts with one segment per lane: the quad kernel (swimmer_quad3.h) and the
-// mirror-quad kernel with lane roles (swimmer_oct3.h), their ARS gate kernels and the mirror-quad safe-exploration
-// kernel.  (One file: the three forms share load_policy_row<8, 2, ...> and the riding covariance tile.)
+// mirror-quad kernel with lane roles (swimmer_oct3.h) and its packed-record form, their ARS gate kernels and the
+// mirror-quad safe-exploration kernel.  (One file: the three forms share load_policy_row<8, 2, ...> and the riding covariance tile.)
 #include "swimmer_cov.h"
 #include "swimmer_quad3.h"
 #include "swimmer_oct3.h"
@@ -75,6 +75,21 @@ ars_gate_oct3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__re
 #define SW_GATE_BODY 1
 #include "swimmer_rollout_oct3.inc"
 #undef SW_GATE_BODY
+}
+
+// The mirror-quad rollout with capture and V2 moments in the PACKED record form (body: swimmer_rollout_octp3.inc): the
+// eight state components of a rollout on its eight lanes, ONE trajectory store and ONE moment pair per step where
+// rollout_oct3_kernel<ARS, true, true> has three stores and six accumulates; same outputs, bit for bit.
+template <bool ARS>
+__global__ void __launch_bounds__(kOctBlock)
+rollout_octp3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                     const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                     const double *__restrict__ mean, const double *__restrict__ inv_std,
+                     const double *__restrict__ state0, double *__restrict__ returns,
+                     double *__restrict__ traj, double *__restrict__ final_state,
+                     double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
+{
+#include "swimmer_rollout_octp3.inc"
 }
 
 // ------------------------------------------------------------------------------------
@@ -279,6 +294,13 @@ namespace sw_launch __attribute__((visibility("hidden"))) {
 int launch_oct3(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H, const RolloutArgs &a,
                 hipStream_t stream, const SideWork *side)
 {
+    // capture + V2 moments: the packed record form, unless SW_FLAG_CAPTURE_SPLIT asks for the three-store kernel
+    if (a.traj && a.moments && !(p->flags & SW_FLAG_CAPTURE_SPLIT)) {
+        with_bools([&](auto ARS) {
+            launch_segment_per_lane(rollout_octp3_kernel<ARS.value>, p, plan, n_roll, H, a, stream, side);
+        }, ars);
+        return launch_status();
+    }
     with_bools([&](auto ARS, auto TRAJ, auto MOM) {
         launch_segment_per_lane(rollout_oct3_kernel<ARS.value, TRAJ.value, MOM.value>, p, plan, n_roll, H, a, stream,
                                 side);

@@ -1,0 +1,200 @@
+// Body of rollout_octp3_kernel (csrc/swimmer_rollout_n3.hip): the mirror-quad rollout of swimmer_rollout_oct3.inc with
+// trajectory capture AND V2 moment sums, in the PACKED record form.  Included INSIDE the kernel's braces.
+//
+// rollout_oct3_kernel<ARS, true, true> records a step with three 8-byte stores (theta and thetadot on quad-A lanes
+// 0..2, Gdot on lane 0 of both quads: 24 + 24 + 16 = 64 live lanes, 128 lane slots dropped by the range check) and six
+// accumulate instructions of which every lane uses at most four.  A store costs a lone wave 12-14 cycles however many
+// of its lanes are live.  Here the eight state components of a rollout sit on its eight lanes, in ONE register Z:
+//
+//   lane of the rollout   Z holds each step                               trajectory column   shift
+//   A0, A1, A2            theta of segment q (the lane's own)             2 + 2q              pi/2
+//   A3 (mirror of A0)     Gdot_x (its own Pu: lane 0's, bit for bit)      0                   0
+//   B0, B1, B2            thetadot of segment q, QUAD A's copy (row_ror:8) 3 + 2q             0
+//   B3 (mirror of B0)     Gdot_y (its own Pu)                             1                   0
+//
+// so a step is recorded by one wave-wide store without a dropped lane, one m1 += X and one m2 = fma(X, X, m2) with
+// X = Z - shift.  Every output has the bits of the three-store kernel: lane 3 of a quad receives what lane 0 receives
+// (seg = 0, kDppNext1 = [1,2,0,1], kDppNext2 = [2,0,1,2]), the B lanes record quad A's thetadot and not their own copy
+// (which differs by rounding), Z - 0.0 is exact, X on A0..A2 is that kernel's `th - pi/2`, and every accumulator sees
+// the same sequence of operands.  Everything ahead of the record (lane layout, policy row, renormalisation, geometry,
+// dynamics, range test, trip structure) is that kernel's, token for token.
+//
+// KEEP THE TWO FILES IN STEP: the shared part is a copy, because the machine code of rollout_oct3_kernel is pinned
+// (tests/test_loop_placement.py) and its body cannot be restructured around a common piece.  Any fix to the shared part
+// must be made in swimmer_rollout_oct3.inc AND here; tests/test_packed_capture_gpu.py (bit identity of the two
+// kernels' outputs) is what notices when they drift apart.
+    side_flag(side);
+    if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
+        side_cov_tile<8, kOctBlock>(side);
+        return;
+    }
+    __builtin_amdgcn_s_setprio(3);   // as in the quad kernel
+    constexpr int D = 8, M = 2;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int q = lane & 3;
+    const int seg = (q == 3) ? 0 : q;              // lane 3 of a quad mirrors lane 0
+    const bool cosine = (lane & 8) != 0;           // quad B of the rollout: cosine / Gdot_y roles
+    const int64_t r_raw = (int64_t)blockIdx.x * kMomGroup + wave * 8 + (lane >> 4) * 2 + ((lane >> 2) & 1);
+    const bool valid = r_raw < n_roll;
+    const int64_t r = valid ? r_raw : n_roll - 1;  // surplus rollouts recompute the last one
+    const sw::OctLane O = sw::oct3_lane(C, seg, cosine);
+    const int cth = 2 + 2 * seg, cthd = 3 + 2 * seg;
+
+    // this lane's policy row in its rotated order [Gdx, Gdy, th_i, thd_i, th_i1, thd_i1, th_i2, thd_i2]
+    const int seg1 = (seg + 1) % 3, seg2 = (seg + 2) % 3;
+    const int cols[D] = {0, 1, cth, cthd, 2 + 2 * seg1, 3 + 2 * seg1, 2 + 2 * seg2, 3 + 2 * seg2};
+    double V[D], nbias;
+    load_policy_row<D, M, ARS>(ARS ? policies : policies + r * (M * D),
+                               ARS ? deltas + (dir_begin + (r >> 1)) * (M * D) : nullptr,
+                               (r & 1) ? -1.0 : 1.0, nu, mean, inv_std, C.c12, seg, cols, V, nbias);
+    // Gdot in the roles: Pu = the component this quad integrates, Pv = its partner's
+    const double VPu = cosine ? V[1] : V[0], VPv = cosine ? V[0] : V[1];
+
+    double gdx = 0.0, gdy = 0.0, th = kHalfPi, thd = 0.0;
+    if (state0) {
+        gdx = state0[r];
+        gdy = state0[n_roll + r];
+        th = state0[(int64_t)cth * n_roll + r];
+        thd = state0[(int64_t)cthd * n_roll + r];
+    }
+    double Pu = cosine ? gdy : gdx, Pv = cosine ? gdx : gdy;
+
+    // the lane's trajectory cell (table above): every lane of the wave stores, nothing is dropped; the surplus
+    // rollouts of the last wave rewrite rollout n_roll - 1's cells with the same values
+    const bool lane3 = q == 3;
+    const int column = lane3 ? (cosine ? 1 : 0) : (cosine ? cthd : cth);
+    const double shift = (!cosine && !lane3) ? kHalfPi : 0.0;
+    const uint32_t voff = (uint32_t)(((int64_t)column * n_roll + r) * 8);
+    const uint32_t slab = (uint32_t)(D * n_roll * 8);
+    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(
+        traj, 0, (int)(uint32_t)((int64_t)H * slab), 0x00020000);
+    uint32_t soff = 0;
+    auto store_cell = [&](double v) {
+        typedef int v2i __attribute__((ext_vector_type(2)));
+        union { double d; v2i i; } u;
+        u.d = v;
+        __builtin_amdgcn_raw_buffer_store_b64(u.i, trs, (int)voff, (int)soff, SW_TRAJ_STORE_AUX);
+    };
+
+    // the angle in reduced form + the polynomial this lane currently evaluates (swimmer_oct3.h)
+    const int designation = cosine ? 1 : 0;
+    double thmax = 0.0, det = 1.0;
+    sw::OctTrig A;
+    A.r = th;
+    A.kd = 0.0;
+    sw::oct3_renorm(A, designation, thmax);
+    double m1 = 0.0, m2 = 0.0;
+    double w1 = sw::dpp_f64<sw::kDppNext1>(thd), w2 = sw::dpp_f64<sw::kDppNext2>(thd);
+    double Th = __builtin_fma(V[2], th, nbias);
+    Th = __builtin_fma(V[4], sw::dpp_f64<sw::kDppNext1>(th), Th);
+    Th = __builtin_fma(V[6], sw::dpp_f64<sw::kDppNext2>(th), Th);
+    const double hV2 = C.h * V[2], hV4 = C.h * V[4], hV6 = C.h * V[6];
+    sw::OctGeo G = sw::oct3_geometry(A), Gn;
+    double magic = 6755399441055744.0;   // 1.5 * 2^52, pinned in a VGPR pair for oct3_keep_reduced
+    asm volatile("" : "+v"(magic));
+    auto one_step = [&](const sw::OctGeo &Gc, sw::OctGeo &Gx) {
+        // theta_{t+1} needs thetadot_t only: advance the angle first and start its range test, the
+        // policy's eight FMAs sit between the vector compare and the scalar branch that waits for it
+        A.r = __builtin_fma(C.h, thd, A.r);
+        const unsigned long long outside = sw::oct3_range_test(A.r);
+        double tq = __builtin_fma(VPu, Pu, Th);
+        tq = __builtin_fma(VPv, Pv, tq);
+        tq = __builtin_fma(V[3], thd, tq);
+        tq = __builtin_fma(V[5], w1, tq);
+        tq = __builtin_fma(V[7], w2, tq);
+        Th = __builtin_fma(hV2, thd, Th);
+        Th = __builtin_fma(hV4, w1, Th);
+        Th = __builtin_fma(hV6, w2, Th);
+        sw::oct3_keep_reduced(A, thmax, magic, designation, outside);   // untaken branch; rare re-normalisation
+        Gx = sw::oct3_geometry(A);
+        det = sw::oct3_dynamics(C, O, Gc, Pu, Pv, thd, w1, w2, tq);
+        // the record: theta_{t+1} straight into Z (the angle itself is not carried in the loop), quad A's new
+        // thetadot onto the B lanes (row_ror:8 under bank mask 0xc: lanes 8..15 of a row), Gdot onto lane 3
+        const double Z = sw::octp3_pack(__builtin_fma(A.kd, sw::kPio2Hi, A.r), thd, Pu, lane3);
+        const double X = Z - shift;
+        m1 += X;
+        m2 = __builtin_fma(X, X, m2);
+        store_cell(Z);
+        soff += slab;
+        w1 = sw::dpp_f64<sw::kDppNext1>(thd);
+        w2 = sw::dpp_f64<sw::kDppNext2>(thd);
+        Pv = sw::dpp_row_f64<sw::kDppRowRor8>(Pu);
+    };
+    // the geometry ping-pongs between G and Gn (no register copies): an even number of steps per trip
+    int32_t t = 0;
+    SW_PIN_LOOP(oct_packed_loop_pad());
+    // eight steps per trip, as in rollout_oct3_kernel (the back edge costs a lone wave ~8-13 ns)
+    for (; t + 8 <= H; t += 8) {
+        one_step(G, Gn);
+        one_step(Gn, G);
+        one_step(G, Gn);
+        one_step(Gn, G);
+        one_step(G, Gn);
+        one_step(Gn, G);
+        one_step(G, Gn);
+        one_step(Gn, G);
+    }
+    for (; t + 4 <= H; t += 4) {
+        one_step(G, Gn);
+        one_step(Gn, G);
+        one_step(G, Gn);
+        one_step(Gn, G);
+    }
+    for (; t + 2 <= H; t += 2) {
+        one_step(G, Gn);
+        one_step(Gn, G);
+    }
+    if (t < H) one_step(G, Gn);
+    if (H > 0) th = __builtin_fma(A.kd, sw::kPio2Hi, A.r);   // the bits of the last step's Z on A0..A2
+    thmax = fmax(thmax, fabs(th));
+
+    // ---- per-rollout outputs: quad A lanes 0..2 hold (theta, thetadot), lane 3 of A the Gdot_x sums, of B Gdot_y's
+    int code = ((det > 0.0) ? 0 : SW_STATUS_SINGULAR) |
+               ((isfinite(th) && isfinite(thd) && isfinite(Pu) && isfinite(Pv)) ? 0 : SW_STATUS_NONFINITE) |
+               ((thmax < sw::kAngleLimit) ? 0 : SW_STATUS_RANGE);
+    // lane 3 computes what lane 0 computes, so with its own code and lanes 1 and 2's it has the quad's
+    code |= __builtin_amdgcn_mov_dpp(code, sw::kDppNext1, 0xf, 0xf, true) |
+            __builtin_amdgcn_mov_dpp(code, sw::kDppNext2, 0xf, 0xf, true);
+    code |= __builtin_amdgcn_mov_dpp(code, sw::kDppRowRor8, 0xf, 0xf, true);
+    const double sg_other = sw::dpp_row_f64<sw::kDppRowRor8>(m1);   // on A3: sum Gdot_y (before the reduction below)
+    if (valid && !cosine && lane3) {
+        const double total = __builtin_fma(C.dirx, m1, C.diry * sg_other);
+        returns[r] = (code & SW_STATUS_RANGE) ? __builtin_nan("") : total;
+        if (status) status[r] = code;
+    }
+    if (final_state && valid) {
+        if (!cosine && q < 3) {
+            final_state[(int64_t)cth * n_roll + r] = th;
+            final_state[(int64_t)cthd * n_roll + r] = thd;
+        }
+        if (q == 0) final_state[(int64_t)(cosine ? 1 : 0) * n_roll + r] = Pu;
+    }
+    {
+        __shared__ double shm[kOctBlock / kWave][16][2];
+        if (!valid) m1 = m2 = 0.0;
+        // sum over the 8 rollouts of the wave, per lane of the rollout: lane bits 2, 4, 5
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int off = (k == 0) ? 4 : (k == 1 ? 16 : 32);
+            m1 += __shfl_xor(m1, off, kWave);
+            m2 += __shfl_xor(m2, off, kWave);
+        }
+        if (lane < 16) {
+            shm[wave][lane][0] = m1;
+            shm[wave][lane][1] = m2;
+        }
+        __syncthreads();
+        // row lanes 0..2: theta sums; 8..10: thetadot sums; 3: Gdot_x sums; 11: Gdot_y sums
+        if (tid < 3) {
+            double *row = moments + (int64_t)blockIdx.x * (2 * D);
+            row[2 + 2 * tid] = shm[0][tid][0] + shm[1][tid][0];
+            row[D + 2 + 2 * tid] = shm[0][tid][1] + shm[1][tid][1];
+            row[3 + 2 * tid] = shm[0][8 + tid][0] + shm[1][8 + tid][0];
+            row[D + 3 + 2 * tid] = shm[0][8 + tid][1] + shm[1][8 + tid][1];
+            if (tid < 2) {
+                const int src = 3 + tid * 8;
+                row[tid] = shm[0][src][0] + shm[1][src][0];
+                row[D + tid] = shm[0][src][1] + shm[1][src][1];
+            }
+        }
+    }
