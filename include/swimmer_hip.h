@@ -35,6 +35,8 @@
  *                        every real step)                            safe_ars/ars.py:111-153
  *   sw_cacla_run_f64     CACLA_agent.run with TwoLayersNet / ActorFA / CriticFA, for every agent of the
  *                        hyper-parameter grid at once   cacla/cacla_agent.py:19-58, :135-199, cacla/swimmer_experiment.py:21-57
+ *   sw_lqr_cacla_run_f64 CACLA_LQR_agent.run and the safe agents' run loops on the LQR environments, one agent per
+ *                        lane   cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py, envs/gym_lqr/lqr_env.py
  *
  * Layouts (d = 2n+2 observation size, m = n-1 action size):
  *   state, SoA    [d][n_env]   field-major: row f holds field f of every env; fields are
@@ -317,6 +319,60 @@ int sw_ars_update_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, 
 int sw_cacla_run_f64(const sw_params *p, int64_t n_agent, int32_t n_iter, int32_t train,
                      const double *gamma, const double *alpha, const double *noise, double *weights,
                      double *state, double *rewards, int32_t *actor_updates, int32_t *status, void *stream);
+
+/* ---- CACLA on LQR, with and without safe exploration (cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py,
+ * envs/gym_lqr/lqr_env.py): whole runs of many independent agents in ONE launch, one agent per lane ----
+ * sw_lqr_cacla_run_f64 runs n_iter steps of the reference's `run` loops for n_agent agents with state dimension ns
+ * (1..SW_LQR_MAX_STATE) and action dimension na (1..SW_LQR_MAX_ACTION).  One step (clip = reset_inbound as coded,
+ * lqr_env.py:80-93: bound M == 0 is no bound, otherwise |x| > M -> |x| / x * M):
+ *   fa = F s;  u = fa + noise[t]
+ *   safe: thr = the agent's fixed one (SW_LQR_THRESHOLD_FIXED), or l - eps_Lc (dA ||s||_2 + dB ||u||_2) (.._STEP; u
+ *         unclipped);  s_sim = clip_s(A_sim s + B_sim clip_a(u) + C_sim);  admitted = cost(s_sim) <= thr
+ *   admitted (always when safe == 0):
+ *         a = clip_a(u);  s' = clip_s(A s + B a + C);  r = -(s'^T Q s' + a^T R a)
+ *         safe and not cost(s') <= l: violations += 1        (the reference prints a line)
+ *         td = r + gamma sum_j V_j s'_j^2 - sum_j V_j s_j^2;  V_j += alpha td s_j^2
+ *         td > 0: F_ij += alpha (u_i - fa_i) s_j  (u unclipped, fa from before);  actor_updates += 1
+ *         last = (s, a, r);  s = s';  admitted += 1
+ *   refused: nothing changes
+ *   record of step t = last, flag SW_LQR_ADMITTED / SW_LQR_REFUSED (last repeats the last admitted step, as the
+ *         reference's lists do) / SW_LQR_NOTHING_YET (refused and nothing admitted so far in the run: no entry)
+ * Arithmetic is not trapped: NaN and inf propagate, a NaN cost refuses, a NaN td updates no actor.
+ * EVERY array is agent-minor ([..][n_agent]): a wave's 64 agents read and write one contiguous run, and the noise and
+ * the records are step-major, so a step's traffic is a handful of such runs.
+ *   params   : [SW_LQR_PARAM_DOUBLES(ns, na)][n_agent]: the real model, the simulator's model (each
+ *              SW_LQR_MODEL_DOUBLES: A [ns][ns] row-major | B [ns][na] | C [ns] | max_s | max_a; C = 0 and bound 0 for
+ *              what an environment does not have), Q [ns][ns], R [na][na], gamma, alpha, l, eps_Lc = epsilon * L_c,
+ *              dA = op_norm_der_A, dB = op_norm_der_B, the fixed simulator threshold.  safe == 0 reads the real
+ *              model, Q, R, gamma and alpha only
+ *   noise    : [n_iter][na][n_agent], added to F s: the caller's N(0, sigma) draws
+ *   F        : in/out [na][ns][n_agent];  V, state: in/out [ns][n_agent]
+ *   last     : in/out [ns + na + 1][n_agent]: the last admitted step's (s, a, r); meaningful once admitted > 0
+ *   counters : in/out int32 [3][n_agent]: admitted, violations, actor_updates; zero them before a run
+ *   status   : in/out int32 [n_agent], |= SW_STATUS_NONFINITE when F, V or the state is not finite after the call
+ *   rec_state [n_iter][ns][n_agent] (the state BEFORE the step), rec_action [n_iter][na][n_agent] (clipped),
+ *   rec_reward [n_iter][n_agent], rec_admitted uint8 [n_iter][n_agent]: each NULL or written at every step
+ * Everything an agent carries is in/out, so a run can be split into launches and the split changes no bit.
+ * cost: SW_LQR_COST_INF max_j |x_j|, SW_LQR_COST_2 sqrt(sum x_j^2), SW_LQR_COST_1 sum |x_j|.
+ * Errors, before any HIP call: a NULL pointer other than a record SW_ERR_NULL; n_agent < 1, n_agent > 2^31 - 1,
+ * n_iter < 0, ns or na out of range SW_ERR_SIZE; safe not 0 / 1, unknown threshold or cost SW_ERR_PARAM.
+ * n_iter = 0 writes nothing. */
+#define SW_LQR_MAX_STATE 4
+#define SW_LQR_MAX_ACTION 2
+#define SW_LQR_MODEL_DOUBLES(ns, na) ((ns) * (ns) + (ns) * (na) + (ns) + 2)
+#define SW_LQR_PARAM_DOUBLES(ns, na) (2 * SW_LQR_MODEL_DOUBLES(ns, na) + (ns) * (ns) + (na) * (na) + 7)
+#define SW_LQR_THRESHOLD_STEP 0  /* CACLA_LQR_SE_agent */
+#define SW_LQR_THRESHOLD_FIXED 1 /* CACLA_LQR_SE_fix, CACLA_Bounded_LQR_SE_agent, CACLA_AffineQR_SE_agent */
+#define SW_LQR_COST_INF 0
+#define SW_LQR_COST_2 1
+#define SW_LQR_COST_1 2
+#define SW_LQR_REFUSED 0
+#define SW_LQR_ADMITTED 1
+#define SW_LQR_NOTHING_YET 2
+int sw_lqr_cacla_run_f64(int32_t ns, int32_t na, int64_t n_agent, int32_t n_iter, int32_t safe, int32_t threshold,
+                         int32_t cost, const double *params, const double *noise, double *F, double *V, double *state,
+                         double *last, int32_t *counters, int32_t *status, double *rec_state, double *rec_action,
+                         double *rec_reward, uint8_t *rec_admitted, void *stream);
 
 /* The same update reading an all-gathered buffer in place (no repacking between the
  * collective and the update):  gathered = `world` segments of

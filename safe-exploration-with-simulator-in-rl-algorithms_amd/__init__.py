@@ -9,6 +9,11 @@ Public surface (mirrors the reference's module layout for this path):
     safe_ars.Basic_ARS / safe_ars.Safe_ARS    safe_ars/ars.py  (batched one-step consumers of the step kernel)
     cacla.CACLA_agent / cacla.CACLABatch      cacla/cacla_agent.py  (whole training runs in one fused launch)
     cacla.swimmer_experiment                  cacla/swimmer_experiment.py  (the whole grid as one batch)
+    cacla.CACLA_LQR_agent, cacla.cacla_safe_agent.*, cacla.CACLA_LQR_Batch
+                                              cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py  (one agent per lane)
+    envs.gym_lqr.lqr_env.*                    envs/gym_lqr/lqr_env.py  (host NumPy)
+    cacla.lqr_experiment / cacla.safe_exploration_lqr / cacla.window
+                                              cacla/lqr_experiment.py, cacla/safe_exploration_lqr.py, cacla/window.py
     kernels.*                                 thin wrappers of the C ABI (include/swimmer_hip.h)
 """
 from . import _build, _lib, kernels  # noqa: F401

@@ -64,6 +64,30 @@ def draw_networks(n, generator=None):
     return nets
 
 
+class Uploader(object):
+    """Double-buffered upload of host chunks (float64 arrays of at most max_elems elements): chunk k + 1 is drawn
+    into one pinned buffer while the copy of chunk k leaves the other and its launch runs (copies and launches are
+    asynchronous on the current stream).  Shared by the swimmer's and the LQR agents' chunk loops."""
+
+    def __init__(self, max_elems, device):
+        self.device = device
+        self.host = [torch.empty(max_elems, dtype=torch.float64).pin_memory() for _ in range(2)]
+        self.copied = [None, None]
+        self.k = 0
+
+    def upload(self, array):
+        i = self.k % 2
+        self.k += 1
+        if self.copied[i] is not None:
+            self.copied[i].synchronize()          # its last upload has left the pinned buffer
+        view = self.host[i][:array.size].view(array.shape)
+        view.numpy()[...] = array
+        out = view.to(self.device, non_blocking=True)
+        self.copied[i] = torch.cuda.Event()
+        self.copied[i].record()
+        return out
+
+
 class _Run(object):
     """The device side of a run of A agents: weights, state, counters and the chunk loop.  draw(c) returns the next
     c steps' noise [A, c, m] on the host; chunk k + 1 is drawn while chunk k runs (launches are asynchronous), and
@@ -90,19 +114,11 @@ class _Run(object):
         if not train and len(sizes) > 1:
             # the actors keep seeing the observation the LAUNCH started from (include/swimmer_hip.h): one launch
             sizes = [n_iter]
-        host = [torch.empty((self.A, max(sizes), m), dtype=torch.float64).pin_memory() for _ in range(2)]
-        copied = [None, None]
         out = []
         with torch.cuda.device(self.device):
-            for k, c in enumerate(sizes):
-                buf = host[k % 2]
-                if copied[k % 2] is not None:
-                    copied[k % 2].synchronize()          # its last upload has left the pinned buffer
-                view = buf.view(-1)[:self.A * c * m].view(self.A, c, m)
-                view.numpy()[...] = draw(c)
-                noise = view.to(self.device, non_blocking=True)
-                copied[k % 2] = torch.cuda.Event()
-                copied[k % 2].record()
+            up = Uploader(self.A * max(sizes) * m, self.device)
+            for c in sizes:
+                noise = up.upload(np.asarray(draw(c), dtype=np.float64).reshape(self.A, c, m))
                 out.append(kernels.cacla_run(self.p, c, train, self.gamma, self.alpha, noise, self.weights,
                                              self.state, actor_updates=self.actor_updates, status=self.status))
             return (out[0] if len(out) == 1 else torch.cat(out, dim=1)).cpu().numpy()
@@ -187,3 +203,46 @@ class CACLABatch(object):
         self.status = run.status.cpu().numpy()
         self.actor_updates = run.actor_updates.cpu().numpy()
         return rewards
+
+
+class CACLA_LQR_agent:
+    """Drop-in for the reference's CACLA_LQR_agent (cacla_agent.py:202-297): CACLA on an LQR environment
+    (envs.gym_lqr) with the linear actor F [n_ac, n_obs] and the quadratic critic V [n_obs], kept across runs.
+    run() is the reference's loop on the fused kernel (sw_lqr_cacla_run_f64, cacla/lqr.py); the host forward and
+    backward methods are the reference's, for evaluating a learnt agent by hand.
+
+    After run(): admitted (steps taken; n_iter here), violations (0 here), actor_updates (steps with temp_diff > 0)
+    and status (SW_STATUS_NONFINITE when F, V or the state overflowed); the environment's state is the run's last."""
+
+    chunk = 2048       # steps per launch
+    device = "cuda:0"
+
+    def __init__(self, env):
+        self.env = env
+        n_obs = env.observation_space.shape[0]
+        n_ac = env.action_space.shape[0]
+        self.F = np.zeros((n_ac, n_obs))
+        self.V = np.zeros(n_obs)
+        self.admitted = self.violations = self.actor_updates = self.status = 0
+
+    def forward_action_FA(self, state):
+        """The linear actor: F s."""
+        return self.F @ np.asarray(state, dtype=np.float64)
+
+    def backward_action_FA(self, alpha, action, state, FA_action):
+        """F_ij += (alpha (action_i - FA_action_i)) state_j."""
+        step = alpha * (np.asarray(action, dtype=np.float64) - np.asarray(FA_action, dtype=np.float64))
+        self.F += np.outer(step, np.asarray(state, dtype=np.float64))
+
+    def forward_value_FA(self, state):
+        """The quadratic critic: sum_j V_j s_j^2."""
+        return self.V @ np.square(np.asarray(state, dtype=np.float64))
+
+    def backward_value_FA(self, alpha, delta, state):
+        """V_j += (alpha delta) s_j^2."""
+        self.V += (alpha * delta) * np.square(np.asarray(state, dtype=np.float64))
+
+    def run(self, n_iter, gamma, alpha, sigma, H=1000):
+        """-> (states [n_iter, n_obs], actions [n_iter, n_ac], rewards [n_iter]), as the reference."""
+        from . import lqr
+        return lqr.run_single(self, "plain", n_iter, gamma, alpha, sigma, H)

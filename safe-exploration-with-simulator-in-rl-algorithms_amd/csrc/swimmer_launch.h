@@ -53,6 +53,10 @@
 //                              (a hidden unit per lane, two from n = 6), the physics redundantly in every lane, the
 //                              n + 1 network outputs of a step summed through LDS in a fixed order and handed out
 //                              with v_readlane; instruction-issue bound like the latency forms
+//   swimmer_lqr.hip (a translation unit of its own)
+//   lqr_cacla_kernel<NS,NA,MODE>  sw_lqr_cacla_run_f64: CACLA on LQR problems (plain, safe with a per-step or a fixed
+//                              simulator threshold), ONE AGENT PER LANE: models, F, V and state in VGPRs, no LDS, no
+//                              cross-lane traffic; agent-minor arrays, the noise loaded a block of steps ahead
 //   swimmer_abi.hip
 //   the rollout entry points and the native ARS iteration pipeline (sw_ars_pipeline_*: copy stream, progress
 //   flag, 4-slot buffer ring; the covariance pass rides along in the next rollout launch)

@@ -644,3 +644,50 @@ class ArsPipeline(object):
             int(rows_chunk), ptr(deltas_dev), ptr(policy), float(alpha), float(b), int(top_b),
             ptr(running), int(n_new_states), ptr(mean), ptr(inv_std), ptr(sigma_out),
             stream_ptr()), "sw_ars_iteration_update_f64")
+
+
+LQR_MAX_STATE, LQR_MAX_ACTION = 4, 2                       # SW_LQR_MAX_STATE, SW_LQR_MAX_ACTION
+LQR_THRESHOLD_STEP, LQR_THRESHOLD_FIXED = 0, 1             # SW_LQR_THRESHOLD_*
+LQR_COST_INF, LQR_COST_2, LQR_COST_1 = 0, 1, 2             # SW_LQR_COST_*
+LQR_REFUSED, LQR_ADMITTED, LQR_NOTHING_YET = 0, 1, 2       # SW_LQR_REFUSED / ADMITTED / NOTHING_YET
+
+
+def lqr_model_doubles(ns: int, na: int) -> int:
+    """SW_LQR_MODEL_DOUBLES: A [ns][ns] | B [ns][na] | C [ns] | max_s | max_a."""
+    return ns * ns + ns * na + ns + 2
+
+
+def lqr_param_doubles(ns: int, na: int) -> int:
+    """SW_LQR_PARAM_DOUBLES: real model | simulator model | Q | R | gamma alpha l eps_Lc dA dB fixed threshold."""
+    return 2 * lqr_model_doubles(ns, na) + ns * ns + na * na + 7
+
+
+def lqr_cacla_run(ns: int, na: int, n_iter: int, safe: bool, threshold: int, cost: int, params, noise, F, V, state,
+                  last, counters, status, rec_state=None, rec_action=None, rec_reward=None, rec_admitted=None):
+    """n_iter steps of CACLA on LQR for A independent agents in ONE launch (sw_lqr_cacla_run_f64), one agent per lane.
+    Every tensor is agent-minor: params [lqr_param_doubles, A], noise [n_iter, na, A], F [na, ns, A], V and state
+    [ns, A], last [ns + na + 1, A], counters int32 [3, A] (admitted, violations, actor_updates) and status int32 [A]
+    are updated in place; the records rec_state [n_iter, ns, A], rec_action [n_iter, na, A], rec_reward [n_iter, A]
+    and rec_admitted uint8 [n_iter, A] are written when given."""
+    require_gpu()
+    if params.dim() != 2 or params.shape[1] < 1:
+        raise _lib.SwimmerHipError(f"params: expected float64 tensor of shape (P, A), got {tuple(params.shape)}")
+    A, dev = params.shape[1], params.device
+    _want(params, "params", (lqr_param_doubles(ns, na), A))
+    _want(noise, "noise", (n_iter, na, A))
+    _want(F, "F", (na, ns, A))
+    _want(V, "V", (ns, A))
+    _want(state, "state", (ns, A))
+    _want(last, "last", (ns + na + 1, A))
+    _want_i32(counters, "counters", (3, A), dev)
+    _want_i32(status, "status", (A,), dev)
+    for t, name, shape in ((rec_state, "rec_state", (n_iter, ns, A)), (rec_action, "rec_action", (n_iter, na, A)),
+                           (rec_reward, "rec_reward", (n_iter, A))):
+        if t is not None:
+            _want(t, name, shape)
+    if rec_admitted is not None and (rec_admitted.dtype != torch.uint8 or tuple(rec_admitted.shape) != (n_iter, A)):
+        raise _lib.SwimmerHipError(f"rec_admitted: expected uint8 tensor of shape {(n_iter, A)}")
+    check(load().sw_lqr_cacla_run_f64(int(ns), int(na), A, int(n_iter), 1 if safe else 0, int(threshold), int(cost),
+                                      ptr(params), ptr(noise), ptr(F), ptr(V), ptr(state), ptr(last), ptr(counters),
+                                      ptr(status), ptr(rec_state), ptr(rec_action), ptr(rec_reward),
+                                      ptr(rec_admitted), stream_ptr()), "sw_lqr_cacla_run_f64")
