@@ -95,6 +95,10 @@ extern "C" {
  * that records with three partly masked stores and six sums instead.  Same outputs bit for bit; for A/B measurements
  * and for tests.  Launches without capture or without moments ignore it. */
 #define SW_FLAG_CAPTURE_SPLIT 8
+/* The same launches record in the packed form through a kernel with a leaner step (store offsets in loop-invariant
+ * scalar registers, range test on vcc).  This bit keeps them on the first packed kernel.  Same outputs bit for bit;
+ * for A/B measurements and for tests.  Together with SW_FLAG_CAPTURE_SPLIT it is SW_ERR_PARAM. */
+#define SW_FLAG_CAPTURE_PACKED_V1 16
 
 /* sw_params.flags: which of the reference's two swimmer models the kernels integrate.
  * Default (bit clear): the Gym env (envs/gym_swimmer/swimmer/remy_swimmer_env.py, explicit

@@ -23,7 +23,10 @@
 //                              8192 rollouts (one wave per SIMD)
 //   rollout_octp3_kernel       the same with capture AND V2 moments in the packed record form: one trajectory store
 //                              and one moment pair per step (swimmer_rollout_octp3.inc); bit-identical outputs;
-//                              SW_FLAG_CAPTURE_SPLIT keeps such a launch on rollout_oct3_kernel<.., true, true>
+//   rollout_octl3_kernel       the packed record form with a leaner step (the same body, SW_OCTP_LEAN 1): store
+//                              offsets from loop-invariant SGPRs, range test on vcc; the default of such a launch.
+//                              SW_FLAG_CAPTURE_PACKED_V1 keeps it on rollout_octp3_kernel,
+//                              SW_FLAG_CAPTURE_SPLIT on rollout_oct3_kernel<.., true, true>
 //   rollout_quad3_kernel       n = 3, one DPP quad per rollout (swimmer_quad3.h): 8193 .. 16384 rollouts
 //   swimmer_rollout_row.hip
 //   rollout_row_kernel<N>      n = 4..8, one segment per lane, one rollout per 16-lane DPP row
@@ -107,6 +110,14 @@ constexpr int oct_loop_pad(bool traj, bool mom) { return traj ? (mom ? 5 : 6) : 
 #define SW_OCTP_LOOP_PAD 4
 #endif
 constexpr int oct_packed_loop_pad() { return SW_OCTP_LOOP_PAD; }
+// its lean mode (rollout_octl3_kernel): other instructions in the loop (5688 bytes), a pad of its own.  Swept over the
+// eight even pads, the ones that start the loop on an 8-byte boundary (profiles/r08_b_octl_pad_sweep.log, two passes):
+// 0.2093-0.2125 ms per launch; 2 and 10 (loop head at offset 0 and 32 of its line) are the best two in both passes
+// (0.2093-0.2101), 2 is pinned.  -DSW_OCTL_LOOP_PAD=k overrides it for a sweep
+#ifndef SW_OCTL_LOOP_PAD
+#define SW_OCTL_LOOP_PAD 2
+#endif
+constexpr int oct_lean_loop_pad() { return SW_OCTL_LOOP_PAD; }
 #ifndef SW_QUAD_LOOP_PAD
 #define SW_QUAD_LOOP_PAD 0
 #endif
@@ -203,7 +214,10 @@ int validate_params(const sw_params *p)
 {
     if (!p) return SW_ERR_NULL;
     if (p->n < 2 || p->n > SW_MAX_SEGMENTS) return SW_ERR_SEGMENTS;
-    if (p->flags & ~(SW_FLAG_ROLLOUT_LANE | SW_FLAG_ROLLOUT_QUAD | SW_FLAG_MODEL_TWIN | SW_FLAG_CAPTURE_SPLIT)) return SW_ERR_PARAM;
+    if (p->flags & ~(SW_FLAG_ROLLOUT_LANE | SW_FLAG_ROLLOUT_QUAD | SW_FLAG_MODEL_TWIN | SW_FLAG_CAPTURE_SPLIT |
+                     SW_FLAG_CAPTURE_PACKED_V1))
+        return SW_ERR_PARAM;
+    if ((p->flags & SW_FLAG_CAPTURE_SPLIT) && (p->flags & SW_FLAG_CAPTURE_PACKED_V1)) return SW_ERR_PARAM;   // one or the other
     if (!(p->l_i > 0.0) || !(p->m_i > 0.0) || !isfinite(p->l_i) || !isfinite(p->m_i) ||
         !isfinite(p->k) || !isfinite(p->h) || !isfinite(p->dir_x) || !isfinite(p->dir_y))
         return SW_ERR_PARAM;

@@ -194,6 +194,87 @@ __device__ __forceinline__ void oct3_keep_reduced(OctTrig &T, double &thmax, dou
         : "scc");
 }
 
+// The same pair with the lane mask in VCC (rollout_octl3_kernel, the lean mode of swimmer_rollout_octp3.inc): the
+// vector compare writes vcc and `s_cbranch_vccnz` branches on it, so the scalar compare that turned the mask of
+// oct3_range_test into SCC is gone -- one issue slot per step, which costs a lone wave as much as an f64 FMA.  The
+// mask travels between the two statements in a variable bound to vcc; should the compiler need vcc in between it
+// moves the mask out and back (correct, slower: the ISA test counts the loop's instructions).  All lanes are active
+// in the loop, so vccnz (some bit of vcc set) is what `s_cmp_lg_u64 mask, 0` was.  SCC is not touched any more.
+// Wait states: the "manually inserted wait states" table of the CDNA3 / CDNA4 ISA guide was NOT at hand when this
+// was written, so nothing here quotes it.  What the form rests on instead: hipcc's own code generation for gfx950
+// puts `s_cbranch_vccnz` DIRECTLY behind the `v_cmp_* vcc` it waits for, without a nop (any `if` on a wave-uniform
+// vector compare compiles to that pair), so the hardware interlocks it as it interlocks the v_cmp -> s_cmp_lg_u64
+// of oct3_keep_reduced; the VCCZ defect the compiler does work around is SMEM-writes-VCC on SI / CI only.  In the
+// built loop 2 to 5 instructions separate the compare from its branch (the compiler moves some of the policy's FMAs
+// away, exactly as it does between the compare and the s_cmp_lg_u64 of rollout_octp3_kernel) -- the source order
+// does NOT guarantee a distance, and the form does not depend on one.  Anyone with the guide at hand: look up "VALU
+// writes VCC" followed by a branch on VCCZ / VCCNZ and replace this paragraph.
+// The out-of-line block below is oct3_keep_reduced's, instruction for instruction: keep the two in step.
+__device__ __forceinline__ unsigned long long oct3_range_test_vcc(double r)
+{
+    register unsigned long long mask asm("vcc");
+    asm volatile("v_cmp_gt_f64_e64 %[m], |%[r]|, %[lim]" : [m] "=s"(mask) : [r] "v"(r), [lim] "s"(kPio4));
+    return mask;
+}
+
+__device__ __forceinline__ void oct3_keep_reduced_vcc(OctTrig &T, double &thmax, double magic, int designation,
+                                                      unsigned long long outside)
+{
+    double t0, t1, t2;
+    int q, q1;
+    register unsigned long long mask asm("vcc") = outside;
+    asm volatile(
+        "s_cbranch_vccnz .Lsw_oct_renorm_%=\n"                // mask: %[m]
+        ".Lsw_oct_reduced_%=:\n\t"
+        ".subsection 1\n"
+        ".Lsw_oct_renorm_%=:\n\t"
+        "v_fma_f64 %[t1], %[r], %[c2opi], %[magic]\n\t"     // k + magic
+        "v_add_f64 %[t0], %[t1], -%[magic]\n\t"             // k = rint(r * 2/pi)
+        "v_fma_f64 %[r], -%[t0], %[hi], %[r]\n\t"           // exact
+        "v_fma_f64 %[r], -%[t0], %[lo], %[r]\n\t"
+        "v_add_f64 %[kd], %[kd], %[t0]\n\t"
+        "v_cvt_i32_f64_e32 %[q], %[kd]\n\t"                 // K (|K| < 2^31 inside the valid range)
+        "v_add_u32_e32 %[q], %[q], %[des]\n\t"              // cos(theta) = sin(theta + pi/2): K + 1
+        "v_and_b32_e32 %[q1], 1, %[q]\n\t"                  // type: 1 = cosine polynomial
+        "v_and_b32_e32 %[q], 2, %[q]\n\t"
+        "v_cvt_f64_i32_e32 %[t0], %[q]\n\t"                 // 0 or 2
+        "v_add_f64 %[t0], 1.0, -%[t0]\n\t"                  // sign
+        "v_cvt_f64_i32_e32 %[t1], %[q1]\n\t"                // type as 0.0 / 1.0
+        "v_mul_f64 %[selC], %[t1], %[t0]\n\t"               // type * sign
+        "v_add_f64 %[selS], %[t0], -%[selC]\n\t"            // (1 - type) * sign
+        "v_add_f64 %[t0], 1.0, -%[t1]\n\t"                  // 1 - type
+        "v_mul_f64 %[t2], %[t0], %[s0]\n\t"
+        "v_fma_f64 %[k0], %[t1], %[c0], %[t2]\n\t"
+        "v_mul_f64 %[t2], %[t0], %[s1]\n\t"
+        "v_fma_f64 %[k1], %[t1], %[c1], %[t2]\n\t"
+        "v_mul_f64 %[t2], %[t0], %[s2]\n\t"
+        "v_fma_f64 %[k2], %[t1], %[c2], %[t2]\n\t"
+        "v_mul_f64 %[t2], %[t0], %[s3]\n\t"
+        "v_fma_f64 %[k3], %[t1], %[c3], %[t2]\n\t"
+        "v_mul_f64 %[t2], %[t0], %[s4]\n\t"
+        "v_fma_f64 %[k4], %[t1], %[c4], %[t2]\n\t"
+        "v_mul_f64 %[t2], %[t0], %[s5]\n\t"
+        "v_fma_f64 %[k5], %[t1], %[c5], %[t2]\n\t"
+        "v_mul_f64 %[t2], %[t0], %[s6]\n\t"
+        "v_fma_f64 %[k6], %[t1], %[c6], %[t2]\n\t"
+        "v_fma_f64 %[t0], %[kd], %[hi], %[r]\n\t"
+        "v_max_f64 %[thmax], %[thmax], |%[t0]|\n\t"
+        "s_branch .Lsw_oct_reduced_%=\n\t"
+        ".subsection 0"
+        : [r] "+v"(T.r), [kd] "+v"(T.kd), [selS] "+v"(T.selS), [selC] "+v"(T.selC), [thmax] "+v"(thmax),
+          [k0] "+v"(T.k[0]), [k1] "+v"(T.k[1]), [k2] "+v"(T.k[2]), [k3] "+v"(T.k[3]), [k4] "+v"(T.k[4]),
+          [k5] "+v"(T.k[5]), [k6] "+v"(T.k[6]),
+          [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [q] "=&v"(q), [q1] "=&v"(q1)
+        : [c2opi] "s"(0.63661977236758134308), [hi] "s"(kPio2Hi), [lo] "s"(kPio2Lo),
+          [magic] "v"(magic), [des] "v"(designation), [m] "s"(mask),
+          [s0] "s"(0.0), [s1] "s"(1.58969099521155010221e-10), [s2] "s"(-2.50507602534068634195e-08),
+          [s3] "s"(2.75573137070700676789e-06), [s4] "s"(-1.98412698298579493134e-04),
+          [s5] "s"(8.33333333332248946124e-03), [s6] "s"(-1.66666666666666324348e-01),
+          [c0] "s"(-1.13596475577881948265e-11), [c1] "s"(2.08757232129817482790e-09),
+          [c2] "s"(-2.75573143513906633035e-07), [c3] "s"(2.48015872894767294178e-05),
+          [c4] "s"(-1.38888888888741095749e-03), [c5] "s"(4.16666666666666019037e-02), [c6] "s"(-0.5));
+}
+
 __device__ __forceinline__ OctLane oct3_lane(const Consts &C, int seg, bool cosine)
 {
     const Quad3Lane L = quad3_lane(seg);

@@ -1,5 +1,7 @@
-// Body of rollout_octp3_kernel (csrc/swimmer_rollout_n3.hip): the mirror-quad rollout of swimmer_rollout_oct3.inc with
-// trajectory capture AND V2 moment sums, in the PACKED record form.  Included INSIDE the kernel's braces.
+// Body of rollout_octp3_kernel and rollout_octl3_kernel (csrc/swimmer_rollout_n3.hip): the mirror-quad rollout of
+// swimmer_rollout_oct3.inc with trajectory capture AND V2 moment sums, in the PACKED record form.  Included INSIDE the
+// kernel's braces, with SW_OCTP_LEAN defined as 0 (rollout_octp3_kernel) or 1 (rollout_octl3_kernel: same record, same
+// arithmetic, less scalar bookkeeping per step -- below, after the note on the two files).
 //
 // rollout_oct3_kernel<ARS, true, true> records a step with three 8-byte stores (theta and thetadot on quad-A lanes
 // 0..2, Gdot on lane 0 of both quads: 24 + 24 + 16 = 64 live lanes, 128 lane slots dropped by the range check) and six
@@ -23,6 +25,24 @@
 // (tests/test_loop_placement.py) and its body cannot be restructured around a common piece.  Any fix to the shared part
 // must be made in swimmer_rollout_oct3.inc AND here; tests/test_packed_capture_gpu.py (bit identity of the two
 // kernels' outputs) is what notices when they drift apart.
+//
+// SW_OCTP_LEAN switches exactly three places of this file, marked `#if SW_OCTP_LEAN`; with 0 the text the compiler sees
+// is the packed kernel's as it was, and its machine code is pinned (tests/test_packed_capture_isa.py):
+//   1. where a store goes.  Packed: scalar offset soff, `soff += slab` after every store (per trip of eight a chain of
+//      eight dependent s_add, and six more that rebuild base + j slab for the next trip).  Lean: the scalar offsets of a
+//      trip's steps are the loop-invariant k_j = j slab, j = 1..7, pinned in SGPRs, and the inline constant 0 for the
+//      trip's first step; the trip's base rides in the VECTOR offset, bumped once per trip (SW_OCTP_TRIP_END: 8 slab
+//      in the main loop, 4 slab and 2 slab in the tail loops, nothing after the single last step; the amounts are
+//      scalars computed ahead of the loops).  Descriptor, num_records and every address are the packed kernel's, and
+//      so is the 32-bit range: the descriptor already assumes H slab < 2^32.
+//   2. the step's position in its trip (SW_OCTP_STEP_AT), which selects that scalar offset.
+//   3. the range test: oct3_range_test_vcc / oct3_keep_reduced_vcc (swimmer_oct3.h) -- the compare writes vcc and
+//      s_cbranch_vccnz reaches the same out-of-line re-normalisation block; no s_cmp_lg_u64.
+// Everything else (lane roles, Z, X = Z - shift, m1, m2, octp3_pack, the epilogue, the riding covariance tile) is one
+// text for both kernels; tests/test_lean_capture_gpu.py compares their outputs bit for bit.
+#ifndef SW_OCTP_LEAN
+#error "define SW_OCTP_LEAN as 0 or 1 before including swimmer_rollout_octp3.inc"
+#endif
     side_flag(side);
     if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
         side_cov_tile<8, kOctBlock>(side);
@@ -69,12 +89,31 @@
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(
         traj, 0, (int)(uint32_t)((int64_t)H * slab), 0x00020000);
     uint32_t soff = 0;
+#if SW_OCTP_LEAN
+    // vrun = voff + (first step of the current trip) slab; soff = (position in the trip) slab: one of k1..k7, or 0
+    uint32_t vrun = voff;
+    uint32_t k1 = slab, k2 = 2 * slab, k3 = 3 * slab, k4 = 4 * slab, k5 = 5 * slab, k6 = 6 * slab, k7 = 7 * slab;
+    uint32_t bump8 = 8 * slab, bump4 = 4 * slab, bump2 = 2 * slab;
+    asm volatile("" : "+s"(k1), "+s"(k2), "+s"(k3), "+s"(k4), "+s"(k5), "+s"(k6), "+s"(k7));
+    asm volatile("" : "+s"(bump8), "+s"(bump4), "+s"(bump2));
+#define SW_OCTP_STEP_AT(K) soff = (K)
+#define SW_OCTP_TRIP_END(BUMP) vrun += (BUMP)
+    auto store_cell = [&](double v) {
+        typedef int v2i __attribute__((ext_vector_type(2)));
+        union { double d; v2i i; } u;
+        u.d = v;
+        __builtin_amdgcn_raw_buffer_store_b64(u.i, trs, (int)vrun, (int)soff, SW_TRAJ_STORE_AUX);
+    };
+#else
+#define SW_OCTP_STEP_AT(K) (void)0
+#define SW_OCTP_TRIP_END(BUMP) (void)0
     auto store_cell = [&](double v) {
         typedef int v2i __attribute__((ext_vector_type(2)));
         union { double d; v2i i; } u;
         u.d = v;
         __builtin_amdgcn_raw_buffer_store_b64(u.i, trs, (int)voff, (int)soff, SW_TRAJ_STORE_AUX);
     };
+#endif
 
     // the angle in reduced form + the polynomial this lane currently evaluates (swimmer_oct3.h)
     const int designation = cosine ? 1 : 0;
@@ -96,7 +135,11 @@
         // theta_{t+1} needs thetadot_t only: advance the angle first and start its range test, the
         // policy's eight FMAs sit between the vector compare and the scalar branch that waits for it
         A.r = __builtin_fma(C.h, thd, A.r);
+#if SW_OCTP_LEAN
+        const unsigned long long outside = sw::oct3_range_test_vcc(A.r);
+#else
         const unsigned long long outside = sw::oct3_range_test(A.r);
+#endif
         double tq = __builtin_fma(VPu, Pu, Th);
         tq = __builtin_fma(VPv, Pv, tq);
         tq = __builtin_fma(V[3], thd, tq);
@@ -105,7 +148,11 @@
         Th = __builtin_fma(hV2, thd, Th);
         Th = __builtin_fma(hV4, w1, Th);
         Th = __builtin_fma(hV6, w2, Th);
+#if SW_OCTP_LEAN
+        sw::oct3_keep_reduced_vcc(A, thmax, magic, designation, outside);
+#else
         sw::oct3_keep_reduced(A, thmax, magic, designation, outside);   // untaken branch; rare re-normalisation
+#endif
         Gx = sw::oct3_geometry(A);
         det = sw::oct3_dynamics(C, O, Gc, Pu, Pv, thd, w1, w2, tq);
         // the record: theta_{t+1} straight into Z (the angle itself is not carried in the loop), quad A's new
@@ -115,36 +162,44 @@
         m1 += X;
         m2 = __builtin_fma(X, X, m2);
         store_cell(Z);
+#if !SW_OCTP_LEAN
         soff += slab;
+#endif
         w1 = sw::dpp_f64<sw::kDppNext1>(thd);
         w2 = sw::dpp_f64<sw::kDppNext2>(thd);
         Pv = sw::dpp_row_f64<sw::kDppRowRor8>(Pu);
     };
     // the geometry ping-pongs between G and Gn (no register copies): an even number of steps per trip
     int32_t t = 0;
-    SW_PIN_LOOP(oct_packed_loop_pad());
+    SW_PIN_LOOP(SW_OCTP_LEAN ? oct_lean_loop_pad() : oct_packed_loop_pad());
     // eight steps per trip, as in rollout_oct3_kernel (the back edge costs a lone wave ~8-13 ns)
     for (; t + 8 <= H; t += 8) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
+        SW_OCTP_STEP_AT(0);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k1); one_step(Gn, G);
+        SW_OCTP_STEP_AT(k2); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k3); one_step(Gn, G);
+        SW_OCTP_STEP_AT(k4); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k5); one_step(Gn, G);
+        SW_OCTP_STEP_AT(k6); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k7); one_step(Gn, G);
+        SW_OCTP_TRIP_END(bump8);
     }
     for (; t + 4 <= H; t += 4) {
-        one_step(G, Gn);
-        one_step(Gn, G);
-        one_step(G, Gn);
-        one_step(Gn, G);
+        SW_OCTP_STEP_AT(0);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k1); one_step(Gn, G);
+        SW_OCTP_STEP_AT(k2); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k3); one_step(Gn, G);
+        SW_OCTP_TRIP_END(bump4);
     }
     for (; t + 2 <= H; t += 2) {
-        one_step(G, Gn);
-        one_step(Gn, G);
+        SW_OCTP_STEP_AT(0);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k1); one_step(Gn, G);
+        SW_OCTP_TRIP_END(bump2);
     }
+    SW_OCTP_STEP_AT(0);
     if (t < H) one_step(G, Gn);
+#undef SW_OCTP_STEP_AT
+#undef SW_OCTP_TRIP_END
     if (H > 0) th = __builtin_fma(A.kd, sw::kPio2Hi, A.r);   // the bits of the last step's Z on A0..A2
     thmax = fmax(thmax, fabs(th));
 

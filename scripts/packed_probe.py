@@ -1,8 +1,10 @@
 """Rollout launch time and iteration time of the headline ARS V2 iteration (n = 3, capture + V2 moments, full covariance
-riding along) in the packed record form ("auto") and the three-store form ("split"), through the native pipeline.
-For the loop-placement sweep of rollout_octp3_kernel (SWIMMER_HIP_LIB=... over builds with -DSW_OCTP_LOOP_PAD=k,
-scripts/ab_probe.sh) and as a same-process cross-check of the two forms.  PK=auto,split chooses the forms, PREPS the
-number of timed blocks of 50 iterations per form (interleaved).  Design aid."""
+riding along) in the packed record form ("auto": with the lean step, rollout_octl3_kernel; "packed_v1": the first packed
+kernel, rollout_octp3_kernel) and the three-store form ("split"), through the native pipeline.  For the loop-placement
+sweeps of the packed kernels (SWIMMER_HIP_LIB=... over builds with -DSW_OCTP_LOOP_PAD=k / -DSW_OCTL_LOOP_PAD=k,
+scripts/ab_probe.sh) and as a same-process cross-check of the forms.  PK=auto,split chooses the forms (default; a
+library from before the lean step knows "auto" and "split" only), PREPS the number of timed blocks of 50 iterations
+per form (interleaved).  Design aid."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
