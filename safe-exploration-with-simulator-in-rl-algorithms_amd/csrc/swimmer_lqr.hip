@@ -42,7 +42,14 @@ __device__ __forceinline__ double lqr_clip(double x, double M)
 template <int NS>
 __device__ __forceinline__ double lqr_cost(const double (&x)[NS], int32_t cost)
 {
-    if (cost == SW_LQR_COST_INF) {
+    // One coordinate: |x_0| whatever the norm (sqrt(x_0^2) where numpy takes it), as ONE select.  Written as the three
+    // branches below, the inf- and the 1-norm are the same expression here, and the compiler's merge of the two left
+    // the 1-norm's value undefined (the gate compared a stale register): tests/test_lqr_matrix_gpu.py, ns = 1,
+    // SW_LQR_COST_1.  The branches are not instantiated for NS == 1.
+    if constexpr (NS == 1) {
+        const double a = fabs(x[0]);
+        return cost == SW_LQR_COST_2 ? sqrt(x[0] * x[0]) : a;
+    } else if (cost == SW_LQR_COST_INF) {
         double m = fabs(x[0]);
 #pragma unroll
         for (int j = 1; j < NS; ++j) {
@@ -50,17 +57,17 @@ __device__ __forceinline__ double lqr_cost(const double (&x)[NS], int32_t cost)
             m = (a > m || a != a) ? a : m;
         }
         return m;
-    }
-    if (cost == SW_LQR_COST_2) {
+    } else if (cost == SW_LQR_COST_2) {
         double q = x[0] * x[0];
 #pragma unroll
         for (int j = 1; j < NS; ++j) q += x[j] * x[j];
         return sqrt(q);
-    }
-    double q = fabs(x[0]);
+    } else {
+        double q = fabs(x[0]);
 #pragma unroll
-    for (int j = 1; j < NS; ++j) q += fabs(x[j]);
-    return q;
+        for (int j = 1; j < NS; ++j) q += fabs(x[j]);
+        return q;
+    }
 }
 
 template <int NS, int NA>

@@ -72,9 +72,10 @@ def clip(x, M):
     """reset_inbound as coded: M == 0 no bound, else |x_i| > M -> |x_i| / x_i * M.  A copy."""
     x = np.array(x, dtype=np.float64)
     if M != 0:
-        with np.errstate(invalid="ignore", divide="ignore"):
-            big = np.abs(x) > M
-            x[big] = np.abs(x[big]) / x[big] * M
+        big = np.abs(x) > M
+        if big.any():
+            with np.errstate(invalid="ignore", divide="ignore"):
+                x[big] = np.abs(x[big]) / x[big] * M
     return x
 
 
@@ -86,9 +87,16 @@ def model(env):
 
 
 def env_step(m, s, u):
+    return step_counted(m, s, u)[:2]
+
+
+def step_counted(m, s, u):
+    """env_step and whether (clip_a changed the action, clip_s changed the state)."""
     A, B, C, max_s, max_a = m
     a = clip(u, max_a)
-    return clip(A @ s + B @ a + C, max_s), a
+    raw = A @ s + B @ a + C
+    sn = clip(raw, max_s)
+    return sn, a, (int(max_a != 0 and bool((a != u).any())), int(max_s != 0 and bool((sn != raw).any())))
 
 
 def run(real, Q, R, gamma, alpha, x0, noise, sim=None, threshold="step", ord=np.inf, l=0.0, eps_lc=0.0, dA=0.0,
@@ -96,7 +104,8 @@ def run(real, Q, R, gamma, alpha, x0, noise, sim=None, threshold="step", ord=np.
     """real, sim: model() tuples (sim None: a plain run); noise [T, na]; threshold "step" | "fixed".  Returns a dict:
     states [T, ns], actions [T, na], rewards [T] and admitted [T] (1 admitted, 0 refused and repeating, 2 refused
     with nothing admitted yet: that row is not meaningful), F, V, state, the counters, and the run's smallest |td|
-    and |cost - threshold| (the distances from a step's discontinuities)."""
+    and |cost - threshold| (the distances from a step's discontinuities), and in how many steps reset_inbound changed
+    a value: clip_a_real, clip_s_real (admitted steps), clip_a_sim, clip_s_sim (every step of a safe run)."""
     Q, R = np.asarray(Q, dtype=np.float64), np.asarray(R, dtype=np.float64)
     ns, na = real[0].shape[1], real[1].shape[1]
     F = np.zeros((na, ns)) if F0 is None else np.array(F0, dtype=np.float64)
@@ -108,6 +117,7 @@ def run(real, Q, R, gamma, alpha, x0, noise, sim=None, threshold="step", ord=np.
     last = (np.zeros(ns), np.zeros(na), 0.0)
     n_adm = n_viol = n_upd = 0
     min_td = min_gap = np.inf
+    clips = np.zeros(4, dtype=np.int64)                          # a real, s real, a sim, s sim
     for t in range(T):
         fa = F @ s
         u = fa + noise[t]
@@ -115,12 +125,14 @@ def run(real, Q, R, gamma, alpha, x0, noise, sim=None, threshold="step", ord=np.
         if sim is not None:
             thr = thr_fixed if threshold == "fixed" else \
                 l - eps_lc * (dA * np.linalg.norm(s, 2) + dB * np.linalg.norm(u, 2))
-            s_sim, _ = env_step(sim, s, u)
+            s_sim, _, how = step_counted(sim, s, u)
+            clips[2:] += how
             c = np.linalg.norm(s_sim, ord)
             min_gap = min(min_gap, abs(c - thr))
             admitted = bool(c <= thr)
         if admitted:
-            sn, a = env_step(real, s, u)
+            sn, a, how = step_counted(real, s, u)
+            clips[:2] += how
             r = -(sn @ Q @ sn + a @ R @ a)
             if sim is not None:
                 c = np.linalg.norm(sn, ord)
@@ -138,7 +150,9 @@ def run(real, Q, R, gamma, alpha, x0, noise, sim=None, threshold="step", ord=np.
         states[t], actions[t], rewards[t] = last
         flags[t] = 1 if admitted else (0 if n_adm else 2)
     return dict(states=states, actions=actions, rewards=rewards, admitted_flags=flags, F=F, V=V, state=s,
-                admitted=n_adm, violations=n_viol, actor_updates=n_upd, min_td=min_td, min_gap=min_gap)
+                admitted=n_adm, violations=n_viol, actor_updates=n_upd, min_td=min_td, min_gap=min_gap,
+                clip_a_real=int(clips[0]), clip_s_real=int(clips[1]), clip_a_sim=int(clips[2]),
+                clip_s_sim=int(clips[3]))
 
 
 def run_case(case, envs, x0, noise):

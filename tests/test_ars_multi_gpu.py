@@ -38,27 +38,31 @@ def _agent_inputs(n, N, S, v2, seed=0):
     return policy, deltas, mean, inv_std
 
 
-def _compare_rollouts(p, n, N, S, v2):
-    """Multi launch (outputs poisoned first) against one ars_rollouts call per agent; returns the number of agents."""
+def _compare_rollouts(p, n, N, S, v2, with_moments=True):
+    """Multi launch (outputs poisoned first) against one ars_rollouts call per agent; returns the number of agents.
+    with_moments False: neither side is given a moments buffer -- the segment-per-lane forms then run their MOM = false
+    kernels -- and returns and status are what is compared."""
     policy, deltas, mean, inv_std = _agent_inputs(n, N, S, v2)
     rows = kernels.moments_blocks(2 * N)
     returns = torch.full((S, 2 * N), float("nan"), dtype=torch.float64, device=DEV)
-    moments = torch.full((S, rows, 2 * p.d), float("nan"), dtype=torch.float64, device=DEV)
+    moments = torch.full((S, rows, 2 * p.d), float("nan"), dtype=torch.float64, device=DEV) if with_moments else None
     status = torch.full((S, 2 * N), -1, dtype=torch.int32, device=DEV)
     out = kernels.ars_rollouts_multi(p, H, policy, deltas, NU, mean, inv_std, returns=returns, moments=moments,
                                      status=status)
     assert out is returns
-    R, M, St = returns.cpu().numpy(), moments.cpu().numpy(), status.cpu().numpy()
-    assert not np.isnan(R).any() and not np.isnan(M).any(), "an output cell was left unwritten"
+    R, St = returns.cpu().numpy(), status.cpu().numpy()
+    M = moments.cpu().numpy() if with_moments else None
+    assert not np.isnan(R).any() and (M is None or not np.isnan(M).any()), "an output cell was left unwritten"
     assert (St == 0).all()
     for a in range(S):
-        mom1 = torch.zeros((rows, 2 * p.d), dtype=torch.float64, device=DEV)
+        mom1 = torch.zeros((rows, 2 * p.d), dtype=torch.float64, device=DEV) if with_moments else None
         st1 = torch.full((2 * N,), -1, dtype=torch.int32, device=DEV)
         r1 = kernels.ars_rollouts(p, H, policy[a], deltas[a], NU, 0, N, None if mean is None else mean[a],
                                   None if inv_std is None else inv_std[a], moments=mom1, status=st1)
         assert (st1.cpu().numpy() == 0).all()
         assert np.array_equal(R[a], r1.cpu().numpy()), (a, "returns")
-        assert np.array_equal(M[a], mom1.cpu().numpy()), (a, "moment rows")
+        if with_moments:
+            assert np.array_equal(M[a], mom1.cpu().numpy()), (a, "moment rows")
     return S
 
 
@@ -71,6 +75,46 @@ def test_multi_rollouts_equal_single_agent_launches(n, N, S, form, v2):
     # auto: S * 16 * ceil(2N / 16) <= 288 slots, far below 8192 -- the batch and the single launches take the same form
     p = sw.SwParams.make(n, 0.8, 1.2, 10.2, 1e-3, flags=sw._lib.kernel_flags(form))
     _compare_rollouts(p, n, N, S, v2)
+
+
+# Every compiled instantiation that the product above does not reach (it always asks for moments, so its segment-per-lane
+# launches are all MOM = true), S = 3 agents each: (form, twin model, n, N, V2, moments asked for).
+#  * ars_multi_row_kernel<N, MOM>, N = 4, 5, 7, 8 (each with a loop pad of its own per MOM): a V1 agent asks for no
+#    moments, MOM = false; a V2 agent does, MOM = true; 2N = 14 and 18: just below and across a moment row.  N = 6 with
+#    MOM = false too, which the product leaves out.  MOM follows the moments pointer alone: one V2 launch without
+#    moments (whitening, MOM = false) at n = 5.
+#  * ars_multi_lane_kernel<N, false> at the same n.
+#  * ars_multi_lane_kernel<N, true>: the twin model (its single-agent rollouts are checked against the C oracle in
+#    tests/test_twin.py; equality with them is the reference here).
+# The n = 3 forms without moments: test_multi_rollouts_without_moments_and_status (mirror-quad) and the quad child.
+MORE_INSTANTIATIONS = [
+    ("auto", False, 4, 7, False, False), ("auto", False, 4, 7, True, True),
+    ("auto", False, 4, 9, False, False), ("auto", False, 4, 9, True, True),
+    ("auto", False, 5, 7, False, False), ("auto", False, 5, 7, True, True),
+    ("auto", False, 5, 9, False, False), ("auto", False, 5, 9, True, True), ("auto", False, 5, 9, True, False),
+    ("auto", False, 6, 7, False, False), ("auto", False, 6, 9, False, False),
+    ("auto", False, 7, 7, False, False), ("auto", False, 7, 7, True, True),
+    ("auto", False, 7, 9, False, False), ("auto", False, 7, 9, True, True),
+    ("auto", False, 8, 7, False, False), ("auto", False, 8, 7, True, True),
+    ("auto", False, 8, 9, False, False), ("auto", False, 8, 9, True, True),
+    ("lane", False, 4, 9, False, True), ("lane", False, 4, 9, True, True),
+    ("lane", False, 5, 9, False, True), ("lane", False, 5, 9, True, True),
+    ("lane", False, 7, 9, False, True), ("lane", False, 7, 9, True, True),
+    ("lane", False, 8, 9, False, True), ("lane", False, 8, 9, True, True),
+    ("lane", True, 2, 9, False, True), ("lane", True, 2, 9, True, True),
+    ("lane", True, 3, 9, False, True), ("lane", True, 3, 9, True, True),
+    ("lane", True, 6, 9, False, True), ("lane", True, 6, 9, True, True),
+    ("lane", True, 8, 9, False, True), ("lane", True, 8, 9, True, True),
+]
+
+
+@pytest.mark.parametrize("form,twin,n,N,v2,with_moments", MORE_INSTANTIATIONS,
+                         ids=[f"{f}-{'twin' if t else 'swimmer'}-n{n}-N{N}-{'V2' if v else 'V1'}-{'mom' if w else 'nomom'}"
+                              for f, t, n, N, v, w in MORE_INSTANTIATIONS])
+def test_multi_rollouts_at_every_compiled_n_and_model(form, twin, n, N, v2, with_moments):
+    flags = sw._lib.kernel_flags(form) | (sw._lib.FLAG_MODEL_TWIN if twin else 0)
+    p = sw.SwParams.make(n, 0.8, 1.2, 10.2, 1e-3, flags=flags)
+    _compare_rollouts(p, n, N, 3, v2, with_moments)
 
 
 def test_multi_rollouts_without_moments_and_status():
@@ -103,6 +147,15 @@ def _update_inputs(rng, S, N, d, m, rows, count):
 @pytest.mark.parametrize("top_b", [0, 4])
 @pytest.mark.parametrize("N", [1, 9, 300])
 def test_multi_update_equals_single_agent_updates(N, top_b, v2):
+    _compare_updates(N, top_b, v2)
+
+
+def test_multi_update_with_wide_workgroups():
+    """N = 1025 directions: the first count at which the update kernels run 1024-thread workgroups (kUpdWideFrom)."""
+    _compare_updates(1025, 4, True)
+
+
+def _compare_updates(N, top_b, v2):
     n, S, count = 3, 3, 40
     p = sw.SwParams.make(n)
     m, d = p.m, p.d
@@ -177,7 +230,9 @@ def test_argument_errors_leave_the_outputs_alone():
 
 
 if __name__ == "__main__" and sys.argv[1:] == ["quad-child"]:
-    # the child of test_quad3_multi_form_in_a_child_process: 2N = 18 crosses a moment row, V1 and V2
+    # the child of test_quad3_multi_form_in_a_child_process: 2N = 18 crosses a moment row, V1 and V2; and V1 without
+    # moments: ars_multi_quad3_kernel<false>
     for v2_ in (False, True):
         _compare_rollouts(sw.SwParams.make(3, 0.8, 1.2, 10.2, 1e-3), 3, 9, 3, v2_)
+    _compare_rollouts(sw.SwParams.make(3, 0.8, 1.2, 10.2, 1e-3), 3, 9, 3, False, with_moments=False)
     print("quad-child ok")
