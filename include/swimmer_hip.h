@@ -24,6 +24,10 @@
  *   sw_ars_rollouts_multi_f64, sw_ars_update_multi_f64
  *                        the same two for every seed of Experiment.plot at once (one Ray actor per seed in the
  *                        reference)                                  ars/experiment.py:61-72
+ *   sw_ars_gate_multi_f64, sw_ars_pack_admitted_f64, sw_ars_rollouts_multi_counted_f64,
+ *   sw_ars_update_multi_counted_f64
+ *                        the safe iteration (ars_agent.py:137-184) for every agent of ars/safe_exploration.py's sweep
+ *                        at once (one Ray actor per agent in the reference)   ars/safe_exploration.py
  *   sw_traj_moments_f64  np.mean / np.cov over the saved states     ars/ars_agent.py:180-182
  *   sw_env1_step         the same step for ONE swimmer handed over in host memory (the Gym
  *                        surface and the RL-Glue env_step, SwimmerEnvironment.cpp:53-68)
@@ -292,6 +296,63 @@ int sw_ars_update_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, 
                             int64_t top_b, const double *moments, int64_t n_moment_rows,
                             double *running, int64_t n_new_states, double *mean, double *inv_std,
                             double *sigma_out, void *stream);
+
+/* ---- safe agents in lock-step: gate, pack, counted rollouts, counted update -- four launches per iteration for ALL
+ * agents, nothing read by the host in between ----
+ * The safe iteration of ARSAgent (ars_agent.py:137-184) is a gate launch, a host read of the admit flags, then rollouts
+ * and update over the k admitted directions.  Here k stays on the device: every agent a has its own simulator,
+ * simulator threshold and count[a], and row a of every result has the bits of the single-agent sequence
+ * sw_ars_gate_f64 -> (pack on the host) -> sw_ars_rollouts_f64 -> sw_ars_update_f64 with n_dir = count[a].
+ * Arrays are agent-major and dense as in sw_ars_rollouts_multi_f64; the form and the grid are chosen as there (from
+ * n_agent and the MAXIMUM n_dir: whole workgroups per agent, blockIdx.y = agent).
+ * Errors of all four, before any HIP call: a NULL required pointer SW_ERR_NULL; n_agent < 1, n_agent > 65535,
+ * n_dir < 1 or H < 0 SW_ERR_SIZE; parameters as everywhere.
+ *
+ * sw_ars_gate_multi_f64: sw_ars_gate_f64 (dir_begin = 0) for n_agent agents in one launch.
+ *   base       : n, h, dir_* and flags of every simulator (its own l_i, m_i, k are validated but not used)
+ *   sim        : [n_agent][3] each agent's simulator (l_i, m_i, k); the constants are derived in the kernel by the
+ *                function the host uses, so they have the host's bits (the convention of sw_step_residual_pop_f64)
+ *   sim_thresh : [n_agent]          admit : [n_agent][n_dir]
+ *   policy, deltas, mean / inv_std, returns (required here), status (may be NULL): as sw_ars_rollouts_multi_f64
+ * An agent whose simulator breaks the parameter rule (SW_ERR_PARAM's) gets SW_STATUS_PARAM in its status entries, NaN
+ * returns and admits nothing; the other agents are unaffected. */
+int sw_ars_gate_multi_f64(const sw_params *base, int64_t n_agent, int64_t n_dir, int32_t H, const double *policy,
+                          const double *deltas, double nu, const double *mean, const double *inv_std,
+                          const double *sim, const double *sim_thresh, int32_t *admit, double *returns,
+                          int32_t *status, void *stream);
+
+/* admit [n_agent][n_dir] (and, where given, the gate's status [n_agent][2 n_dir]: a direction with a non-zero status
+ * on either of its simulator rollouts counts as refused -- its NaN return would have admitted it) ->
+ *   count  : int32 [n_agent]          the admitted directions k
+ *   order  : int32 [n_agent][n_dir]   their indices in ascending order in entries 0..k-1, -1 behind them
+ *   packed : [n_agent][n_dir][m][d]   their deltas in that order in entries 0..k-1; the rest is not written
+ * One workgroup per agent; a prefix sum over the flags (ballot and popcount per 64 directions), so the order never
+ * depends on timing.  p gives n only. */
+int sw_ars_pack_admitted_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const int32_t *admit,
+                             const int32_t *status, const double *deltas, int32_t *count, int32_t *order,
+                             double *packed, void *stream);
+
+/* sw_ars_rollouts_multi_f64 with each agent's direction count read from count [n_agent] on the device (values
+ * outside 0..n_dir are clamped); n_dir is the maximum and sets the strides of every array.  Agent a runs 2 count[a]
+ * rollouts of its first count[a] deltas and writes returns and status entries 0..2 count[a] - 1 and moment rows
+ * 0..ceil(2 count[a] / 16) - 1, with the bits of sw_ars_rollouts_f64(n_dir = count[a]) in the same form; everything
+ * behind them is left as it was.  Workgroups behind an agent's last rollout return at once. */
+int sw_ars_rollouts_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const int32_t *count,
+                                      int32_t H, const double *policy, const double *deltas, double nu,
+                                      const double *mean, const double *inv_std, double *returns, double *moments,
+                                      int32_t *status, void *stream);
+
+/* sw_ars_update_multi_f64 with per-agent n_dir = count[a], top_b = min(top_b, count[a]), n_new_states =
+ * 2 count[a] H and the agent's ceil(2 count[a] / 16) written moment rows; n_dir and n_moment_rows (>=
+ * sw_moments_blocks(2 n_dir) with V2) are the maxima and set the strides.  Each agent's result has the bits of
+ * sw_ars_update_f64 on its slices with n_dir = count[a].  An agent with count 0 is left untouched: policy, running,
+ * mean, inv_std and sigma_out keep their values.  (From 1025 directions on the single-agent update runs in wider
+ * workgroups: two launches then, each serving the agents whose count picks its width.) */
+int sw_ars_update_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const int32_t *count,
+                                    int32_t H, const double *returns, const double *deltas, double *policy,
+                                    double alpha, double b, int64_t top_b, const double *moments,
+                                    int64_t n_moment_rows, double *running, double *mean, double *inv_std,
+                                    double *sigma_out, void *stream);
 
 /* ---- CACLA (cacla/cacla_agent.py): whole training runs of many independent agents in ONE launch ----
  * An agent is n networks -- the n - 1 actors of ActorFA (one per torque), then the critic of CriticFA -- each a

@@ -5,6 +5,7 @@ Public surface (mirrors the reference's module layout for this path):
     ars.Environment                           ars/environment.py
     ars.ARSAgent                              ars/ars_agent.py
     ars.Experiment                            ars/experiment.py  (its seeds train as one ars.ARSAgentBatch)
+    ars.SafeARSAgentBatch / ars.safe_exploration.run   ars/safe_exploration.py  (every safe agent of the sweep in one batch)
     ars.EnvParam / ars.ARSParam               ars/parameters.py
     safe_ars.Basic_ARS / safe_ars.Safe_ARS    safe_ars/ars.py  (batched one-step consumers of the step kernel)
     cacla.CACLA_agent / cacla.CACLABatch      cacla/cacla_agent.py  (whole training runs in one fused launch)
@@ -19,9 +20,10 @@ Public surface (mirrors the reference's module layout for this path):
 from . import _build, _lib, kernels  # noqa: F401
 from ._lib import SwParams, SwimmerHipError  # noqa: F401
 from .envs import SwimmerEnv, VecSwimmerEnv  # noqa: F401
-from .ars import ARSAgent, ARSAgentBatch, ARSParam, EnvParam, Environment, Experiment  # noqa: F401
+from .ars import (ARSAgent, ARSAgentBatch, ARSParam, EnvParam, Environment, Experiment,  # noqa: F401
+                  SafeARSAgentBatch)
 from . import safe_ars  # noqa: F401
 from . import cacla  # noqa: F401
 
-__all__ = ["SwParams", "SwimmerHipError", "SwimmerEnv", "VecSwimmerEnv", "ARSAgent", "ARSAgentBatch", "ARSParam",
+__all__ = ["SwParams", "SwimmerHipError", "SwimmerEnv", "VecSwimmerEnv", "ARSAgent", "ARSAgentBatch", "SafeARSAgentBatch", "ARSParam",
            "EnvParam", "Environment", "Experiment", "kernels"]

@@ -105,6 +105,21 @@ _PROTOTYPES = {
                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p]),
+    # the safe half of a batch of agents: gate, pack, counted rollouts, counted update
+    "sw_ars_gate_multi_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
+                              + [ctypes.c_void_p] * 8),
+    "sw_ars_pack_admitted_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+                                 + [ctypes.c_void_p] * 7),
+    "sw_ars_rollouts_multi_counted_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_double]
+                                          + [ctypes.c_void_p] * 6),
+    "sw_ars_update_multi_counted_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                                       ctypes.c_double, ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_int64] + [ctypes.c_void_p] * 5),
     "sw_cacla_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
                          + [ctypes.c_void_p] * 9),
     "sw_lqr_cacla_run_f64": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 4

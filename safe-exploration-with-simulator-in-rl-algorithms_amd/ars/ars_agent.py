@@ -70,6 +70,27 @@ def approximate_env_param(env_param, approx_error):
     return env_param
 
 
+def approximate_env_params(env_param, approx_error, count, rng=None):
+    """`count` simulators for the agents of a batch (SafeARSAgentBatch): agent s gets the approximation branch above
+    on ITS OWN copy of `env_param`, as each Ray actor of the reference's ars/safe_exploration.py does on the copy it
+    was sent.  The draws are rand(3) each, taken in agent order from `rng` (a RandomState; default: NumPy's global
+    generator), with the arithmetic of approximate_env_param, so agent 0 is what approximate_env_param gives under
+    the same generator state.  `env_param` itself is not touched."""
+    import copy
+    rand = np.random.rand if rng is None else rng.rand
+    out = []
+    for _ in range(int(count)):
+        sim = copy.copy(env_param)
+        delta = rand(3)
+        delta = delta / np.linalg.norm(delta, ord=2) * approx_error
+        sim.name = 'LeonSwimmer-Simulator'
+        sim.m_i += delta[0]
+        sim.l_i += delta[1]
+        sim.k += delta[2]
+        out.append(sim)
+    return out
+
+
 def simulator_threshold(agent_param, real_env_param, sim_thresh):
     """threshold + alpha(H) * epsilon (ars_agent.py:59-63)."""
     alpha = sim_thresh.compute_alpha(agent_param.H)

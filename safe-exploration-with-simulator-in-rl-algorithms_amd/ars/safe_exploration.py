@@ -1,0 +1,111 @@
+"""The reference's ars/safe_exploration.py without Ray: how tight a simulator threshold safe ARS on the swimmer needs,
+as a sweep over the Lipschitz constant A and the approximation error epsilon.
+
+The script trains a hand controller (unsafe ARS, one seed) in the real world, takes l = 0.99 x its final mean return
+as the safety threshold, and then, for every A and every epsilon, n_seed safe agents that start from the hand
+controller's policy, each with a simulator perturbed by epsilon and the simulator threshold l + alpha_A(H) epsilon
+(ars/parameters.py Threshold.compute_alpha).  The reference starts one Ray actor per agent, 8 at a time; here
+
+  * the hand controller goes through Experiment (one ARSAgentBatch of one seed), and
+  * EVERY (A, epsilon, seed) safe agent -- 4 x 10 x 8 = 320 with the reference's sizes -- trains in ONE
+    SafeARSAgentBatch: they share the real world, H, N and nu and differ in seed, simulator and simulator threshold
+    only.  Agent (A, epsilon, seed) is, bit for bit, ARSAgent(safe=True, seed=seed) with that simulator.
+
+The simulators: in the reference every actor perturbs its own copy of the real parameters with rand(3) from a freshly
+started process's generator; here they are approximate_env_params(..., approx_error=epsilon) draws from `rng`, taken
+in the order of the loops (A, then epsilon, then seed).
+
+run() returns the numbers the reference plots and writes its four figures (one per A) when matplotlib imports.
+Every size is an argument; the defaults are the reference's.
+"""
+import os
+
+import numpy as np
+
+from .ars_agent import approximate_env_params
+from .experiment import Experiment
+from .parameters import ARSParam, EnvParam, Threshold
+from .safe_agent_batch import SafeARSAgentBatch
+
+
+def real_world(H=1000, epsilon=0.001):
+    """The reference's real world (safe_exploration.py:22-24)."""
+    return EnvParam('LeonSwimmer-RealWorld', n=3, H=H, l_i=.8, m_i=1.2, h=1e-3, k=10.2, epsilon=epsilon)
+
+
+def sweep_agents(l, H, A_values, epsilons, n_seed, K, B, rng=None):
+    """The agents of the sweep in batch order [A][epsilon][seed]: (seeds, sim_params, sim_thresholds, and per A the
+    sim_thresh_range over the epsilons)."""
+    seeds, sims, sim_thresholds, ranges = [], [], [], []
+    for A in A_values:
+        alpha = Threshold(K=K, A=A, B=B).compute_alpha(H)
+        ranges.append(np.array([l + alpha * e for e in epsilons]))
+        for epsilon in epsilons:
+            sims += approximate_env_params(real_world(H, epsilon), epsilon, n_seed, rng)
+            seeds += list(range(n_seed))
+            sim_thresholds += [l + alpha * epsilon] * n_seed
+    return seeds, sims, sim_thresholds, ranges
+
+
+def run(*, A_values=(0.1, 0.3, 0.5, 0.7), epsilons=None, n_seed=8, n_iter=400, hand_iter=200, H=1000, K=1, B=0.001,
+        N=1, b=1, alpha=0.0075, nu=0.01, results_path="results/", data_path="ars/data/", rng=None, device=None):
+    """The whole script.  Returns a dict: l, epsilons, A_values, and per A (lists in the order of A_values)
+    min_return [n_eps], max_mean_returns [n_eps], sim_thresh_range [n_eps]; r_graphs [A][eps][seed][n_iter + 1].
+    Files: data_path + saved_hand_policy.npy and threshold.txt, the hand controller's Experiment files under
+    results_path, and results_path + epsilon_sim_threshold_H=.._K=.._A=.._B=...png per A."""
+    epsilons = np.linspace(0.0001, 0.01, 10) if epsilons is None else np.asarray(epsilons, dtype=np.float64)
+    A_values = list(A_values)
+    results_path, data_path = os.path.join(results_path, ""), os.path.join(data_path, "")   # Experiment appends to it
+    os.makedirs(results_path, exist_ok=True)
+    os.makedirs(data_path, exist_ok=True)
+    ep = real_world(H)
+
+    # the initial weights, as if from a hand controller (safe_exploration.py:28-36)
+    hand_agent = ARSParam('HandControl', V1=True, n_iter=hand_iter, H=H, N=N, b=b, alpha=alpha, nu=nu, safe=False,
+                          threshold=0, initial_w='Zero')
+    policy_path = os.path.join(data_path, "saved_hand_policy")
+    returns = Experiment(ep, results_path=results_path, save_policy_path=policy_path).plot(n_seed=1,
+                                                                                           agent_param=hand_agent)
+    # the safety threshold from the known controller (:39-42)
+    l = float(np.mean(returns, axis=0)[-1] * 0.99)
+    print(f"\nSafety threshold: {l}")
+    np.savetxt(os.path.join(data_path, "threshold.txt"), np.array([l]))
+
+    # every safe agent of the sweep in one batch (:54-82)
+    seeds, sims, sim_thresholds, ranges = sweep_agents(l, H, A_values, epsilons, n_seed, K, B, rng)
+    real_agent = ARSParam('RLControl', V1=True, n_iter=n_iter, H=H, N=N, b=b, alpha=alpha, nu=nu, safe=True,
+                          threshold=l, initial_w=policy_path + ".npy")
+    batch = SafeARSAgentBatch(ep, real_agent, seeds, sims, sim_thresholds, device=device)
+    curves = batch.runTraining()
+    r_graphs = curves.reshape(len(A_values), len(epsilons), n_seed, n_iter + 1)
+    out = dict(l=l, epsilons=epsilons, A_values=A_values, r_graphs=r_graphs, sim_thresh_range=ranges,
+               min_return=[], max_mean_returns=[], violations=batch.violations.reshape(r_graphs.shape[:3]))
+    for g in r_graphs:
+        out["min_return"].append(np.array([np.nanmin(r) for r in g]))                       # :80
+        out["max_mean_returns"].append(np.array([np.nanmax(np.mean(r, axis=0)) for r in g]))   # :81-82
+    _figures(out, H, K, B, results_path)
+    return out
+
+
+def _figures(out, H, K, B, results_path):
+    """The reference's figure per A (safe_exploration.py:85-100) on Agg canvases of their own, as Experiment._figures
+    draws its own; skipped when matplotlib does not import."""
+    try:
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+    except ImportError:
+        return
+    eps, l = out["epsilons"], out["l"]
+    for i, A in enumerate(out["A_values"]):
+        fig = Figure(figsize=(10, 8))
+        FigureCanvasAgg(fig)
+        axes = fig.add_subplot(111)
+        axes.plot(eps, out["min_return"][i], marker='o', label="Minimum return")
+        axes.plot(eps, out["max_mean_returns"][i], marker='o', label="Max of mean learning curve")
+        axes.plot(eps, out["sim_thresh_range"][i], linestyle='--', marker='D', label="Simulator threshold")
+        axes.plot(eps, [l] * len(eps), color='black', linewidth=2, label="Safety threshold")
+        axes.legend()
+        axes.set_xlabel("epsilon")
+        axes.set_ylabel("Average return")
+        axes.set_title(f"Safe ARS with approximation error of epsilon, with constants H={H}, K={K}, A={A}, B={B}")
+        fig.savefig(os.path.join(results_path, f"epsilon_sim_threshold_H={H}_K={K}_A={A}_B={B}.png"))

@@ -262,6 +262,71 @@ int sw_ars_rollouts_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir
     return launch_multi_lane(p, plan, n_agent, n_roll, H, a, nu, st);
 }
 
+// The safe half of a batch of agents.  Both entry points choose the form and the grid as sw_ars_rollouts_multi_f64
+// does (from the slot count of the whole launch, at the maximum n_dir for the counted rollouts: a form must not
+// depend on values the host has not seen).
+static int plan_safe_multi(const sw_params *p, int64_t n_agent, int64_t n_dir, int32_t H, RolloutPlan *plan)
+{
+    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;
+    if (n_agent > 65535 || n_dir > ((int64_t)1 << 23)) return SW_ERR_SIZE;
+    const int64_t n_roll = 2 * n_dir;
+    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
+    *plan = plan_rollouts(p, slots, H, false);
+    const dim3 grid = multi_grid(*plan, n_agent, n_roll);
+    if ((int64_t)grid.x * grid.y * plan->block >= ((int64_t)1 << 32)) return SW_ERR_SIZE;   // threads of one launch
+    return SW_OK;
+}
+
+int sw_ars_gate_multi_f64(const sw_params *base, int64_t n_agent, int64_t n_dir, int32_t H, const double *policy,
+                          const double *deltas, double nu, const double *mean, const double *inv_std,
+                          const double *sim, const double *sim_thresh, int32_t *admit, double *returns,
+                          int32_t *status, void *stream)
+{
+    int rc = check_params(base);
+    if (rc) return rc;
+    RolloutPlan plan;
+    rc = plan_safe_multi(base, n_agent, n_dir, H, &plan);
+    if (rc) return rc;
+    if (!policy || !deltas || !sim || !sim_thresh || !admit || !returns) return SW_ERR_NULL;
+    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
+    const SafeMultiArgs a{policy, deltas, mean, inv_std, returns, /*moments=*/nullptr, status, sim, sim_thresh, admit,
+                          /*count=*/nullptr};
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t n_roll = 2 * n_dir;
+    switch (plan.form) {
+    case Form::Oct3: return launch_gate_multi_oct3(base, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Quad3: return launch_gate_multi_quad3(base, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Row: return launch_gate_multi_row(base, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Lane: break;
+    }
+    return launch_gate_multi_lane(base, plan, n_agent, n_roll, H, a, nu, st);
+}
+
+int sw_ars_rollouts_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const int32_t *count,
+                                      int32_t H, const double *policy, const double *deltas, double nu,
+                                      const double *mean, const double *inv_std, double *returns, double *moments,
+                                      int32_t *status, void *stream)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    RolloutPlan plan;
+    rc = plan_safe_multi(p, n_agent, n_dir, H, &plan);
+    if (rc) return rc;
+    if (!count || !policy || !deltas || !returns) return SW_ERR_NULL;
+    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
+    const SafeMultiArgs a{policy, deltas, mean, inv_std, returns, moments, status, /*sim=*/nullptr,
+                          /*sim_thresh=*/nullptr, /*admit=*/nullptr, count};
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t n_roll = 2 * n_dir;
+    switch (plan.form) {
+    case Form::Oct3: return launch_counted_oct3(p, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Quad3: return launch_counted_quad3(p, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Row: return launch_counted_row(p, plan, n_agent, n_roll, H, a, nu, st);
+    case Form::Lane: break;
+    }
+    return launch_counted_lane(p, plan, n_agent, n_roll, H, a, nu, st);
+}
+
 // ---- ARS iteration pipeline ---------------------------------------------------------
 // Host-side enqueue logic of one ARS iteration in native code: the caller's stream (the
 // critical path: rollouts -> [all-gather] -> update), a copy stream for the H2D of the deltas,

@@ -43,10 +43,17 @@
 //                              at the slices of agent blockIdx.y: per rollout the arithmetic of the
 //                              single-agent kernel without capture, hot loops pinned by the body's SW_PIN_LOOP with
 //                              pads of their own (*_multi_loop_pad below)
+//   ars_gate_multi_{oct3,quad3,row,lane}_kernel, ars_counted_{oct3,quad3,row,lane}_kernel  (in the form's file)
+//                              sw_ars_gate_multi_f64 / sw_ars_rollouts_multi_counted_f64: the safe half of a batch of
+//                              agents.  The gate form takes every agent's simulator constants and threshold from device
+//                              arrays (the view derives C with sw::consts_of), the counted form every agent's number
+//                              of rollouts; both are the form's body behind swimmer_rollout_multi.inc
 //   swimmer_update.hip
 //   ars_update_kernel          sigma_R, policy step, V2 statistics merge; pure latency between
 //                              two rollout launches: one round of loads, then LDS only
 //   ars_update_multi_kernel    the same body (swimmer_update.inc) for many agents, grid (m*d + 1, n_agent)
+//   ars_update_counted_kernel  the same with every agent's direction count read on the device (0: agent untouched)
+//   ars_pack_admitted_kernel   admit flags -> count, ascending order, packed deltas; one workgroup per agent
 //   swimmer_cov.hip, swimmer_cov.h
 //   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound; its tile code
 //                              (swimmer_cov.h) also rides along in the segment-per-lane rollout launches (SideJob)
@@ -155,6 +162,31 @@ constexpr int row_multi_loop_pad(int n, bool mom)
 {
     return n == 4 ? (mom ? 1 : 3) : n == 5 ? (mom ? 11 : 15) : n == 6 ? (mom ? 11 : 13) : n == 7 ? (mom ? 10 : 1)
                                                                                                  : (mom ? 9 : 4);
+}
+#endif
+
+// The multi-agent gate kernels (ars_gate_multi_*_kernel) and the counted multi-agent rollout kernels
+// (ars_counted_*_kernel) of the safe batch have prologues of their own again.  Their pads are NOT swept: each puts the
+// hot loop at the offset its single-agent twin has in the same build (the form's gate kernel, resp. the form's ARS
+// kernel without capture, same n, same MOM); scripts/multi_loop_offsets.py prints both offsets for these pairs too.
+// -DSW_SAFE_MULTI_LOOP_PAD=k overrides all of them.
+#ifdef SW_SAFE_MULTI_LOOP_PAD
+constexpr int oct_gate_multi_loop_pad() { return SW_SAFE_MULTI_LOOP_PAD; }
+constexpr int quad_gate_multi_loop_pad() { return SW_SAFE_MULTI_LOOP_PAD; }
+constexpr int row_gate_multi_loop_pad(int) { return SW_SAFE_MULTI_LOOP_PAD; }
+constexpr int oct_counted_loop_pad(bool) { return SW_SAFE_MULTI_LOOP_PAD; }
+constexpr int quad_counted_loop_pad(bool) { return SW_SAFE_MULTI_LOOP_PAD; }
+constexpr int row_counted_loop_pad(int, bool) { return SW_SAFE_MULTI_LOOP_PAD; }
+#else
+constexpr int oct_gate_multi_loop_pad() { return 2; }
+constexpr int quad_gate_multi_loop_pad() { return 0; }
+constexpr int row_gate_multi_loop_pad(int n) { return n == 4 ? 10 : n == 5 ? 4 : n == 6 ? 12 : n == 7 ? 0 : 7; }
+constexpr int oct_counted_loop_pad(bool mom) { return mom ? 12 : 11; }
+constexpr int quad_counted_loop_pad(bool) { return 3; }
+constexpr int row_counted_loop_pad(int n, bool mom)
+{
+    return n == 4 ? (mom ? 14 : 0) : n == 5 ? (mom ? 8 : 12) : n == 6 ? (mom ? 8 : 10) : n == 7 ? (mom ? 10 : 14)
+                                                                                             : (mom ? 6 : 1);
 }
 #endif
 
@@ -294,6 +326,27 @@ __device__ __forceinline__ void gate_store(double ret, int code, bool owner, int
         if (status) status[r] = code;
         if ((r & 1) == 0) admit[r >> 1] = (!(ret <= thr) && !(partner <= thr)) ? 1 : 0;
     }
+}
+
+// A value every lane of the wave holds, moved to scalar registers (the per-agent constants of the safe batch's gate
+// are derived in the kernel from a device array: the bodies expect them where kernel arguments live).
+__device__ __forceinline__ double uniform_f64(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                            __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+__device__ __forceinline__ sw::Consts uniform_consts(const sw::Consts &c)
+{
+    return sw::Consts{uniform_f64(c.l),       uniform_f64(c.h),       uniform_f64(c.dirx),
+                      uniform_f64(c.diry),    uniform_f64(c.kl_nm),   uniform_f64(c.h_kl_nm),
+                      uniform_f64(c.six_k_m), uniform_f64(c.kl_m),    uniform_f64(c.c12)};
+}
+
+// the parameter rule of validate_params for a parameter set read on the device
+__device__ __forceinline__ bool sim_params_ok(double l, double m, double k)
+{
+    return l > 0.0 && m > 0.0 && isfinite(l) && isfinite(m) && isfinite(k);
 }
 
 // This lane's pre-combined policy row V_i = c12 (W_{i-1} - W_i), W = (P +- nu delta) diag(inv_std)
@@ -451,6 +504,22 @@ inline dim3 multi_grid(const RolloutPlan &plan, int64_t n_agent, int64_t n_roll)
     const int per = form_slots(plan.form);
     return dim3((unsigned)((n_roll + per - 1) / per), (unsigned)n_agent);
 }
+// The safe half of a batch of agents (sw_ars_gate_multi_f64, sw_ars_rollouts_multi_counted_f64): MultiArgs plus, for
+// the gate, every agent's simulator (sim [n_agent][3] = l_i, m_i, k), simulator threshold and admit flags
+// [n_agent][n_dir]; for the counted rollouts every agent's direction count [n_agent] (n_roll is then the maximum and
+// sets the strides).  A struct of its own: MultiArgs is a kernel argument of the ars_multi_* kernels as it is.
+struct SafeMultiArgs {
+    const double *policy, *deltas, *mean, *inv_std;
+    double *returns, *moments;
+    int32_t *status;
+    const double *sim, *sim_thresh;
+    int32_t *admit;
+    const int32_t *count;
+};
+using SafeMultiLauncher = int(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                              const SafeMultiArgs &a, double nu, hipStream_t stream);
+SafeMultiLauncher launch_gate_multi_oct3, launch_gate_multi_quad3, launch_gate_multi_row, launch_gate_multi_lane;
+SafeMultiLauncher launch_counted_oct3, launch_counted_quad3, launch_counted_row, launch_counted_lane;
 // Safe exploration (sw_safe_rollouts_f64); there is no safe quad kernel.
 using SafeLauncher = int(const sw_params *real, const sw_params *sim, const RolloutPlan &plan, int64_t n_roll,
                          int32_t H, const double *policies, int32_t cost_kind, int32_t cost_index, double sim_thresh,

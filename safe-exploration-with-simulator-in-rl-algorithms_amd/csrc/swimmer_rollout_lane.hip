@@ -58,6 +58,38 @@ ars_multi_lane_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll, int32_t H,
 #include "swimmer_rollout_lane.inc"
 #undef SW_GATE_BODY
 }
+
+// sw_ars_gate_multi_f64 and sw_ars_rollouts_multi_counted_f64 in the lane form (the view's header has the two modes).
+// The twin model's constants of an agent's simulator are its (l_i, m_i, k) as they are.
+#define SW_MULTI_SLOTS kRollBlock
+#define SW_MULTI_GATE 1
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_multi_lane_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::SafeMultiArgs all, double nu)
+{
+    constexpr bool ARS = true;
+#include "swimmer_rollout_multi.inc"
+    const sw::TwinConsts T{sim_l, sim_m, sim_k, base.h, base.dirx, base.diry};
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_GATE
+
+#define SW_MULTI_COUNTED 1
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+ars_counted_lane_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll_max, int32_t H, sw_launch::SafeMultiArgs all,
+                        double nu)
+{
+    constexpr bool ARS = true;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_COUNTED
+#undef SW_MULTI_SLOTS
 #undef SW_MULTI_N
 
 // ------------------------------------------------------------------------------------
@@ -217,6 +249,28 @@ int launch_multi_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_age
     const sw::TwinConsts T = make_twin_consts(p);
     const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
         hipLaunchKernelGGL((ars_multi_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
+                           dim3(plan.block), 0, stream, C, T, n_roll, H, a, nu);
+    }, is_twin(p));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_gate_multi_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                           const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
+        hipLaunchKernelGGL((ars_gate_multi_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
+                           dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu);
+    }, is_twin(p));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_counted_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                        const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    const sw::Consts C = make_consts(p);
+    const sw::TwinConsts T = make_twin_consts(p);
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
+        hipLaunchKernelGGL((ars_counted_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
                            dim3(plan.block), 0, stream, C, T, n_roll, H, a, nu);
     }, is_twin(p));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;

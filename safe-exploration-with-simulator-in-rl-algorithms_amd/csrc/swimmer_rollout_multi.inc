@@ -5,17 +5,54 @@
 // agent-major arrays in `all` (sw_launch::MultiArgs), n_roll stays the rollouts PER AGENT, and the body then indexes,
 // pads (surplus slots recompute the agent's last rollout and store nothing) and reduces its moment rows exactly as
 // in a single-agent launch: workgroup-uniform base pointers, no moment row with two agents' states.
+//
+// Two more views for the safe batch (`all` is a sw_launch::SafeMultiArgs there):
+//   SW_MULTI_COUNTED 1 (sw_ars_rollouts_multi_counted_f64): the kernel's argument is n_roll_max, which sets the
+//     strides; n_roll = 2 count[agent] is read here.  A workgroup behind the agent's last rollout -- every workgroup
+//     of an agent with count 0 -- returns at once: the test is workgroup-uniform and sits in front of every barrier.
+//     SW_MULTI_SLOTS = the rollouts a workgroup of the form has lanes for.
+//   SW_MULTI_GATE 1 (sw_ars_gate_multi_f64): the kernel's argument is `base` (n, h, direction); C comes from the
+//     agent's (l_i, m_i, k) in all.sim through sw::consts_of -- the host's bits -- and gate_thr / admit are the
+//     agent's.  A parameter set that breaks the parameter rule: SW_STATUS_PARAM, NaN returns, nothing admitted.
     constexpr int kAgentD = 2 * (SW_MULTI_N) + 2, kAgentM = (SW_MULTI_N) - 1;
     const int64_t agent = blockIdx.y;
+#if SW_MULTI_COUNTED
+    const int32_t agent_dirs = __builtin_amdgcn_readfirstlane(all.count[agent]);
+    const int64_t n_roll = 2 * (int64_t)(agent_dirs < 0 ? 0 : (agent_dirs > (n_roll_max >> 1) ? (n_roll_max >> 1) : agent_dirs));
+    if ((int64_t)blockIdx.x * (SW_MULTI_SLOTS) >= n_roll) return;
+#define SW_MULTI_STRIDE n_roll_max
+#else
+#define SW_MULTI_STRIDE n_roll
+#endif
     const double *__restrict__ const policies = all.policy + agent * (kAgentM * kAgentD);
-    const double *__restrict__ const deltas = all.deltas + agent * (n_roll >> 1) * (kAgentM * kAgentD);
+    const double *__restrict__ const deltas = all.deltas + agent * (SW_MULTI_STRIDE >> 1) * (kAgentM * kAgentD);
     const double *__restrict__ const mean = all.mean ? all.mean + agent * kAgentD : nullptr;
     const double *__restrict__ const inv_std = all.inv_std ? all.inv_std + agent * kAgentD : nullptr;
-    double *__restrict__ const returns = all.returns + agent * n_roll;
+    double *__restrict__ const returns = all.returns + agent * SW_MULTI_STRIDE;
+#if SW_MULTI_GATE
+    double *const moments = nullptr;
+#else
     double *__restrict__ const moments =
-        all.moments ? all.moments + agent * ((n_roll + kMomGroup - 1) / kMomGroup) * (2 * kAgentD) : nullptr;
-    int32_t *__restrict__ const status = all.status ? all.status + agent * n_roll : nullptr;
+        all.moments ? all.moments + agent * ((SW_MULTI_STRIDE + kMomGroup - 1) / kMomGroup) * (2 * kAgentD) : nullptr;
+#endif
+    int32_t *__restrict__ const status = all.status ? all.status + agent * SW_MULTI_STRIDE : nullptr;
+#undef SW_MULTI_STRIDE
     constexpr int64_t dir_begin = 0;
     const double *const state0 = nullptr;
     double *const traj = nullptr;
     double *const final_state = nullptr;
+#if SW_MULTI_GATE
+    int32_t *__restrict__ const admit = all.admit + agent * (n_roll >> 1);
+    const double gate_thr = uniform_f64(all.sim_thresh[agent]);
+    const double sim_l = all.sim[agent * 3], sim_m = all.sim[agent * 3 + 1], sim_k = all.sim[agent * 3 + 2];
+    if (!sim_params_ok(sim_l, sim_m, sim_k)) {   // uniform; in front of every barrier
+        const int64_t r_bad = (int64_t)blockIdx.x * (SW_MULTI_SLOTS) + threadIdx.x;
+        if ((int)threadIdx.x < (SW_MULTI_SLOTS) && r_bad < n_roll) {
+            returns[r_bad] = __builtin_nan("");
+            if (status) status[r_bad] = SW_STATUS_PARAM;
+            if ((r_bad & 1) == 0) admit[r_bad >> 1] = 0;
+        }
+        return;
+    }
+    const sw::Consts C = uniform_consts(sw::consts_of(SW_MULTI_N, sim_l, sim_m, sim_k, base.h, base.dirx, base.diry));
+#endif

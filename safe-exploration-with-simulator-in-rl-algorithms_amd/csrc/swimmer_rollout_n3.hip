@@ -138,6 +138,69 @@ ars_multi_oct3_kernel(sw::Consts C, int64_t n_roll, int32_t H, sw_launch::MultiA
 #include "swimmer_rollout_oct3.inc"
 #undef SW_GATE_BODY
 }
+
+// sw_ars_gate_multi_f64 and sw_ars_rollouts_multi_counted_f64 in the two n = 3 forms: the safe half of a batch of
+// agents.  The gate kernels are the form's body with SW_GATE_BODY 1 behind the view with SW_MULTI_GATE 1 (C, gate_thr
+// and admit per agent); the counted kernels are ars_multi_*_kernel with the agent's rollout count read in the view.
+#define SW_MULTI_SLOTS kMomGroup
+#define SW_MULTI_GATE 1
+#define SW_MULTI_PAD quad_gate_multi_loop_pad()
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_multi_quad3_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::SafeMultiArgs all, double nu,
+                            SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_quad3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+
+#define SW_MULTI_PAD oct_gate_multi_loop_pad()
+__global__ void __launch_bounds__(kOctBlock)
+ars_gate_multi_oct3_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::SafeMultiArgs all, double nu,
+                           SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_oct3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+#undef SW_MULTI_GATE
+
+#define SW_MULTI_COUNTED 1
+#define SW_MULTI_PAD quad_counted_loop_pad(MOM)
+template <bool MOM>
+__global__ void __launch_bounds__(kRollBlock)
+ars_counted_quad3_kernel(sw::Consts C, int64_t n_roll_max, int32_t H, sw_launch::SafeMultiArgs all, double nu,
+                         SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_quad3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+
+#define SW_MULTI_PAD oct_counted_loop_pad(MOM)
+template <bool MOM>
+__global__ void __launch_bounds__(kOctBlock)
+ars_counted_oct3_kernel(sw::Consts C, int64_t n_roll_max, int32_t H, sw_launch::SafeMultiArgs all, double nu,
+                        SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_oct3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+#undef SW_MULTI_COUNTED
+#undef SW_MULTI_SLOTS
 #undef SW_MULTI_N
 
 // ------------------------------------------------------------------------------------
@@ -372,6 +435,42 @@ int launch_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_ag
 {
     with_bools([&](auto MOM) {
         hipLaunchKernelGGL(ars_multi_quad3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
+                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    }, a.moments != nullptr);
+    return launch_status();
+}
+
+int launch_gate_multi_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                           const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ars_gate_multi_oct3_kernel, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0, stream,
+                       make_consts(p), n_roll, H, a, nu, kNoSide);
+    return launch_status();
+}
+
+int launch_gate_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                            const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ars_gate_multi_quad3_kernel, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0, stream,
+                       make_consts(p), n_roll, H, a, nu, kNoSide);
+    return launch_status();
+}
+
+int launch_counted_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                        const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    with_bools([&](auto MOM) {
+        hipLaunchKernelGGL(ars_counted_oct3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
+                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    }, a.moments != nullptr);
+    return launch_status();
+}
+
+int launch_counted_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                         const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    with_bools([&](auto MOM) {
+        hipLaunchKernelGGL(ars_counted_quad3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
                            stream, make_consts(p), n_roll, H, a, nu, kNoSide);
     }, a.moments != nullptr);
     return launch_status();

@@ -110,7 +110,9 @@
     };
     // the geometry ping-pongs between G and Gn (no register copies): an even number of steps per trip
     int32_t t = 0;
-#ifdef SW_MULTI_N   // a multi-agent kernel: its own pad (swimmer_launch.h)
+#if defined(SW_MULTI_PAD)   // a gate-multi / counted kernel of the safe batch: its own pad (swimmer_launch.h)
+    SW_PIN_LOOP(SW_MULTI_PAD);
+#elif defined(SW_MULTI_N)   // a multi-agent kernel: its own pad (swimmer_launch.h)
     SW_PIN_LOOP(oct_multi_loop_pad(MOM));
 #else
     SW_PIN_LOOP(oct_loop_pad(TRAJ, MOM));

@@ -138,7 +138,9 @@
     // four steps per trip, the geometry ping-pongs between G and Gn (no register copies)
     int32_t t = 0;
 #if SW_QUAD_UNROLL == 4
-#ifdef SW_MULTI_N   // a multi-agent kernel: its own pad (swimmer_launch.h)
+#if defined(SW_MULTI_PAD)   // a gate-multi / counted kernel of the safe batch: its own pad (swimmer_launch.h)
+    SW_PIN_LOOP(SW_MULTI_PAD);
+#elif defined(SW_MULTI_N)   // a multi-agent kernel: its own pad (swimmer_launch.h)
     SW_PIN_LOOP(quad_multi_loop_pad(MOM));
 #else
     SW_PIN_LOOP(SW_QUAD_LOOP_PAD);

@@ -58,6 +58,42 @@ ars_multi_row_kernel(sw::Consts C, int64_t n_roll, int32_t H, sw_launch::MultiAr
 #include "swimmer_rollout_row.inc"
 #undef SW_GATE_BODY
 }
+
+// sw_ars_gate_multi_f64 and sw_ars_rollouts_multi_counted_f64 in the row form, n = 4..8 (the view's header has the
+// two modes).
+#define SW_MULTI_SLOTS kMomGroup
+#define SW_MULTI_GATE 1
+#define SW_MULTI_PAD row_gate_multi_loop_pad(N)
+template <int N>
+__global__ void __launch_bounds__(kRowBlock, (N <= 6 ? 2 : 1))
+ars_gate_multi_row_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::SafeMultiArgs all, double nu,
+                          SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_row.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+#undef SW_MULTI_GATE
+
+#define SW_MULTI_COUNTED 1
+#define SW_MULTI_PAD row_counted_loop_pad(N, MOM)
+template <int N, bool MOM>
+__global__ void __launch_bounds__(kRowBlock, (N <= 6 ? 2 : 1))
+ars_counted_row_kernel(sw::Consts C, int64_t n_roll_max, int32_t H, sw_launch::SafeMultiArgs all, double nu,
+                       SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 0
+#include "swimmer_rollout_row.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+#undef SW_MULTI_COUNTED
+#undef SW_MULTI_SLOTS
 #undef SW_MULTI_N
 
 // ------------------------------------------------------------------------------------
@@ -254,6 +290,26 @@ int launch_multi_row(const sw_params *p, const RolloutPlan &plan, int64_t n_agen
 {
     const bool known_n = with_n<4, 8>(p->n, [&](auto N, auto MOM) {
         hipLaunchKernelGGL((ars_multi_row_kernel<N.value, MOM.value>), multi_grid(plan, n_agent, n_roll),
+                           dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    }, a.moments != nullptr);
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_gate_multi_row(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                          const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    const bool known_n = with_n<4, 8>(p->n, [&](auto N) {
+        hipLaunchKernelGGL((ars_gate_multi_row_kernel<N.value>), multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
+                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+    });
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
+int launch_counted_row(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
+                       const SafeMultiArgs &a, double nu, hipStream_t stream)
+{
+    const bool known_n = with_n<4, 8>(p->n, [&](auto N, auto MOM) {
+        hipLaunchKernelGGL((ars_counted_row_kernel<N.value, MOM.value>), multi_grid(plan, n_agent, n_roll),
                            dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu, kNoSide);
     }, a.moments != nullptr);
     return known_n ? launch_status() : SW_ERR_SEGMENTS;

@@ -111,7 +111,9 @@
         return __any((4.0 * C.h) * fabs(thd) > sw::kTripSlack);
     };
     int32_t t = 0;
-#ifdef SW_MULTI_N   // a multi-agent kernel: its own pad (swimmer_launch.h)
+#if defined(SW_MULTI_PAD)   // a gate-multi / counted kernel of the safe batch: its own pad (swimmer_launch.h)
+    SW_PIN_LOOP(SW_MULTI_PAD);
+#elif defined(SW_MULTI_N)   // a multi-agent kernel: its own pad (swimmer_launch.h)
     SW_PIN_LOOP(row_multi_loop_pad(N, MOM));
 #else
     SW_PIN_LOOP(row_loop_pad(N, TRAJ, MOM));

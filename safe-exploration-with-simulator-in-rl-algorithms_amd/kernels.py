@@ -444,6 +444,124 @@ def ars_update_multi(p: SwParams, returns, deltas, policy, alpha: float, b: floa
     return policy
 
 
+def _multi_shapes(p, policy, deltas, mean, inv_std):
+    """(S, N, device) of a multi-agent launch's policy [S, m, d] and deltas [S, N, m, d], checked with mean / inv_std."""
+    if policy.dim() != 3 or policy.shape[0] < 1:
+        raise _lib.SwimmerHipError(f"policy: expected float64 tensor of shape (S, m, d), got {tuple(policy.shape)}")
+    S = policy.shape[0]
+    _want(policy, "policy", (S, p.m, p.d))
+    if deltas.dim() != 4 or deltas.shape[1] < 1:
+        raise _lib.SwimmerHipError(f"deltas: expected float64 tensor of shape (S, N, m, d), got {tuple(deltas.shape)}")
+    N = deltas.shape[1]
+    _want(deltas, "deltas", (S, N, p.m, p.d))
+    if (mean is None) != (inv_std is None):
+        raise _lib.SwimmerHipError("mean and inv_std must be given together")
+    if mean is not None:
+        _want(mean, "mean", (S, p.d))
+        _want(inv_std, "inv_std", (S, p.d))
+    return S, N, policy.device
+
+
+def ars_gate_multi(p_base: SwParams, H: int, policy, deltas, nu: float, sim, sim_thresh, mean=None, inv_std=None,
+                   returns=None, status=None, admit=None):
+    """ars_gate for S agents in ONE launch (sw_ars_gate_multi_f64), every agent in a simulator and against a threshold
+    of its own: policy [S, m, d], deltas [S, N, m, d], sim [S, 3] = each agent's (l_i, m_i, k), sim_thresh [S];
+    n, h, the direction and the flags of every simulator come from p_base.  Returns admit (int32 [S, N]); `returns`
+    ([S, 2N]) and `status` (int32 [S, 2N]) receive the simulator returns and status codes, row a as ars_gate gives
+    them for agent a.  A simulator that breaks the parameter rule: SW_STATUS_PARAM, nothing admitted."""
+    require_gpu()
+    S, N, dev = _multi_shapes(p_base, policy, deltas, mean, inv_std)
+    _want(sim, "sim", (S, 3))
+    _want(sim_thresh, "sim_thresh", (S,))
+    returns = _f64((S, 2 * N), dev) if returns is None else _want(returns, "returns", (S, 2 * N))
+    if status is not None:
+        _want_i32(status, "status", (S, 2 * N), dev)
+    admit = (torch.empty((S, N), dtype=torch.int32, device=dev) if admit is None
+             else _want_i32(admit, "admit", (S, N), dev))
+    check(load().sw_ars_gate_multi_f64(ctypes.byref(p_base), S, N, H, ptr(policy), ptr(deltas), float(nu), ptr(mean),
+                                       ptr(inv_std), ptr(sim), ptr(sim_thresh), ptr(admit), ptr(returns),
+                                       ptr(status), stream_ptr()), "sw_ars_gate_multi_f64")
+    return admit
+
+
+def ars_pack_admitted(p: SwParams, admit, deltas, status=None, count=None, order=None, packed=None):
+    """The gate's flags into what the counted launches read (sw_ars_pack_admitted_f64): admit int32 [S, N] (and the
+    gate's status int32 [S, 2N]: a direction with a failed simulator rollout counts as refused), deltas [S, N, m, d]
+    -> (count int32 [S], order int32 [S, N]: the admitted indices ascending, then -1, packed [S, N, m, d]: their
+    deltas in that order in entries 0..count-1; the entries behind them are not written)."""
+    require_gpu()
+    if admit.dim() != 2 or admit.shape[0] < 1 or admit.shape[1] < 1:
+        raise _lib.SwimmerHipError(f"admit: expected int32 tensor of shape (S, N), got {tuple(admit.shape)}")
+    S, N = admit.shape
+    dev = deltas.device
+    _want_i32(admit, "admit", (S, N), dev)
+    _want(deltas, "deltas", (S, N, p.m, p.d))
+    if status is not None:
+        _want_i32(status, "status", (S, 2 * N), dev)
+    count = torch.empty(S, dtype=torch.int32, device=dev) if count is None else _want_i32(count, "count", (S,), dev)
+    order = (torch.empty((S, N), dtype=torch.int32, device=dev) if order is None
+             else _want_i32(order, "order", (S, N), dev))
+    packed = torch.zeros_like(deltas) if packed is None else _want(packed, "packed", (S, N, p.m, p.d))
+    check(load().sw_ars_pack_admitted_f64(ctypes.byref(p), S, N, ptr(admit), ptr(status), ptr(deltas), ptr(count),
+                                          ptr(order), ptr(packed), stream_ptr()), "sw_ars_pack_admitted_f64")
+    return count, order, packed
+
+
+def ars_rollouts_multi_counted(p: SwParams, H: int, policy, deltas, nu: float, count, mean=None, inv_std=None,
+                               returns=None, moments=None, status=None):
+    """ars_rollouts_multi with every agent's direction count read on the device (sw_ars_rollouts_multi_counted_f64):
+    count int32 [S]; agent a runs the 2 count[a] rollouts of its first count[a] deltas and writes returns / status
+    entries 0..2 count[a] - 1 and its first moments_blocks(2 count[a]) moment rows; everything behind is left as it
+    was (a new `returns` starts as NaN).  N = deltas.shape[1] is the maximum and sets the strides."""
+    require_gpu()
+    S, N, dev = _multi_shapes(p, policy, deltas, mean, inv_std)
+    _want_i32(count, "count", (S,), dev)
+    if moments is not None:
+        _want(moments, "moments", (S, moments_blocks(2 * N), 2 * p.d))
+    if status is not None:
+        _want_i32(status, "status", (S, 2 * N), dev)
+    if returns is None:
+        returns = torch.full((S, 2 * N), float("nan"), dtype=torch.float64, device=dev)
+    else:
+        _want(returns, "returns", (S, 2 * N))
+    check(load().sw_ars_rollouts_multi_counted_f64(ctypes.byref(p), S, N, ptr(count), H, ptr(policy), ptr(deltas),
+                                                   float(nu), ptr(mean), ptr(inv_std), ptr(returns), ptr(moments),
+                                                   ptr(status), stream_ptr()), "sw_ars_rollouts_multi_counted_f64")
+    return returns
+
+
+def ars_update_multi_counted(p: SwParams, H: int, count, returns, deltas, policy, alpha: float, b: float,
+                             top_b: int = 0, moments=None, running=None, mean=None, inv_std=None, sigma_out=None):
+    """ars_update_multi with per-agent n_dir = count[a], top_b = min(top_b, count[a]) and n_new_states =
+    2 count[a] H (sw_ars_update_multi_counted_f64), in place; an agent with count 0 is left untouched.  Shapes as
+    ars_update_multi with N the maximum; moments [S, rows >= moments_blocks(2N), 2d]."""
+    require_gpu()
+    if returns.dim() != 2 or returns.shape[0] < 1 or returns.shape[1] < 2 or returns.shape[1] % 2:
+        raise _lib.SwimmerHipError(f"returns: expected float64 tensor of shape (S, 2N), got {tuple(returns.shape)}")
+    S, n_dir = returns.shape[0], returns.shape[1] // 2
+    _want(returns, "returns", (S, 2 * n_dir))
+    _want(policy, "policy", (S, p.m, p.d))
+    _want(deltas, "deltas", (S, n_dir, p.m, p.d))
+    _want_i32(count, "count", (S,), policy.device)
+    n_rows = 0
+    if running is not None:
+        _want(running, "running", (S, 1 + 2 * p.d))
+        _want(mean, "mean", (S, p.d))
+        _want(inv_std, "inv_std", (S, p.d))
+        if moments is None or moments.dim() != 3 or moments.shape[1] < moments_blocks(2 * n_dir):
+            raise _lib.SwimmerHipError("moments: expected float64 tensor of shape (S, rows >= moments_blocks(2N), 2d) "
+                                       "next to running")
+        n_rows = moments.shape[1]
+        _want(moments, "moments", (S, n_rows, 2 * p.d))
+    if sigma_out is not None:
+        _want(sigma_out, "sigma_out", (S,))
+    check(load().sw_ars_update_multi_counted_f64(ctypes.byref(p), S, n_dir, ptr(count), H, ptr(returns), ptr(deltas),
+                                                 ptr(policy), float(alpha), float(b), int(top_b), ptr(moments), n_rows,
+                                                 ptr(running), ptr(mean), ptr(inv_std), ptr(sigma_out), stream_ptr()),
+          "sw_ars_update_multi_counted_f64")
+    return policy
+
+
 CACLA_HIDDEN = 12   # SW_CACLA_HIDDEN: the reference's hidden width (cacla_agent.py:165-166)
 
 

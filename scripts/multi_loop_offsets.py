@@ -1,4 +1,5 @@
-"""Where the hot loops of the multi-agent rollout kernels (ars_multi_*_kernel) sit in their 64-byte code line, next to
+"""Where the hot loops of the multi-agent rollout kernels (ars_multi_*_kernel, and the safe batch's
+ars_gate_multi_*_kernel and ars_counted_*_kernel) sit in their 64-byte code line, next to
 their single-agent twins (the form's ARS kernel without capture, same n, same MOM), from the built library (no GPU).
 
     python scripts/multi_loop_offsets.py
@@ -22,6 +23,16 @@ PAIRS = [("ars_multi_oct3_kernelILb1E", "rollout_oct3_kernelILb1ELb0ELb1E", 0),
          ("ars_multi_quad3_kernelILb0E", "rollout_quad3_kernelILb1ELb0ELb0E", 0)]
 # the row kernel's hot loop is the one-step loop inside a trip: the second largest back edge
 PAIRS += [(f"ars_multi_row_kernelILi{n}ELb{mom}E", f"rollout_row_kernelILi{n}ELb1ELb0ELb{mom}E", 1)
+          for n in range(4, 9) for mom in (1, 0)]
+# the safe batch: the multi-agent gate kernels next to the form's single-agent gate kernel, the counted multi-agent
+# rollout kernels next to the form's ARS kernel without capture (csrc/swimmer_launch.h, *_gate_multi_loop_pad and
+# *_counted_loop_pad)
+PAIRS += [("ars_gate_multi_oct3_kernel", "ars_gate_oct3_kernel", 0),
+          ("ars_gate_multi_quad3_kernel", "ars_gate_quad3_kernel", 0)]
+PAIRS += [(f"ars_gate_multi_row_kernelILi{n}E", f"ars_gate_row_kernelILi{n}E", 1) for n in range(4, 9)]
+PAIRS += [(f"ars_counted_oct3_kernelILb{mom}E", f"rollout_oct3_kernelILb1ELb0ELb{mom}E", 0) for mom in (1, 0)]
+PAIRS += [(f"ars_counted_quad3_kernelILb{mom}E", f"rollout_quad3_kernelILb1ELb0ELb{mom}E", 0) for mom in (1, 0)]
+PAIRS += [(f"ars_counted_row_kernelILi{n}ELb{mom}E", f"rollout_row_kernelILi{n}ELb1ELb0ELb{mom}E", 1)
           for n in range(4, 9) for mom in (1, 0)]
 
 
@@ -57,7 +68,7 @@ def main():
         hm, bm, cm = hot_loop(kernel(lines, multi), which)
         hs, bs, cs = hot_loop(kernel(lines, single), which, like=bm)
         diff = {k: (cs[k], cm[k]) for k in set(cm) | set(cs) if cm[k] != cs[k]}
-        print(f"{multi:32s} {bm:5d} bytes at {hm % 64:2d} | twin {bs:5d} bytes at {hs % 64:2d} | "
+        print(f"{multi:36s} {bm:5d} bytes at {hm % 64:2d} | twin {bs:5d} bytes at {hs % 64:2d} | "
               f"pad {((hs - hm) % 64) // 4:+d} (mod 16) | opcode counts {'equal' if not diff else diff}")
 
 
