@@ -37,6 +37,9 @@
  *                        Estimator.estimate_real_env_param's search)  ars/estimator.py:36-62, :89-110
  *   sw_safe_rollouts_f64 Safe_ARS.isSafe + Safe_ARS.rollout (the one-step simulator look-ahead that gates
  *                        every real step)                            safe_ars/ars.py:111-153
+ *   sw_safe_ars_rollouts_multi_f64
+ *                        Basic_ARS.rollout / Safe_ARS.rollout for the 2N perturbed policies of every agent of
+ *                        safe_ars/experiment.py at once                safe_ars/ars.py:20-31, :111-153, :84-94
  *   sw_cacla_run_f64     CACLA_agent.run with TwoLayersNet / ActorFA / CriticFA, for every agent of the
  *                        hyper-parameter grid at once   cacla/cacla_agent.py:19-58, :135-199, cacla/swimmer_experiment.py:21-57
  *   sw_lqr_cacla_run_f64 CACLA_LQR_agent.run and the safe agents' run loops on the LQR environments, one agent per
@@ -353,6 +356,49 @@ int sw_ars_update_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t
                                     double alpha, double b, int64_t top_b, const double *moments,
                                     int64_t n_moment_rows, double *running, double *mean, double *inv_std,
                                     double *sigma_out, void *stream);
+
+/* ---- safe_ars/experiment.py: Basic_ARS and Safe_ARS agents in lock-step, the per-step gate inside the rollout ----
+ * sw_safe_ars_rollouts_multi_f64: the 2 n_dir exploration rollouts of n_agent agents in one launch, every rollout with
+ * the semantics of sw_safe_rollouts_f64 -- H steps from the reset state, action policy @ obs (V1), every real step gated
+ * by the one-step simulator look-ahead -- with three differences:
+ *   - rollout 2j / 2j+1 of agent a runs the policy P_a + / - nu delta_{a,j}, formed in the kernel with the rounding
+ *     of sw_ars_rollouts_f64 (NumPy's `P + nu * delta` / `P - nu * delta`, bit for bit);
+ *   - the gate is per agent: gated[a] == 0 is Basic_ARS.rollout (safe_ars/ars.py:20-31), every step is taken and the
+ *     look-ahead is not computed -- no threshold and no NaN cost stops such a rollout;
+ *   - every gated agent has its own simulator and simulator threshold, every agent its own real threshold.
+ * No trajectory is stored: the experiment reads its states as cost(state) only (safe_ars/experiment.py:81-82).
+ *   real          : the real swimmer (n, l_i, m_i, k, h, dir_*; SW_FLAG_ROLLOUT_* honoured; Gym model)
+ *   policy        : [n_agent][m][d]         deltas : [n_agent][n_dir][m][d]
+ *   gated         : [n_agent]  0: Basic_ARS.rollout; else Safe_ARS.rollout
+ *   sim           : [n_agent][3] (l_i, m_i, k) of each agent's simulator, read for gated agents only; the constants
+ *                   are derived in the kernel by the function the host uses (as in sw_ars_gate_multi_f64)
+ *   sim_thresh    : [n_agent], read for gated agents only; a NaN refuses step 0 (cost <= NaN is false)
+ *   real_thresh   : [n_agent]
+ *   cost_kind, cost_index : SW_COST_* as sw_safe_rollouts_f64
+ *   returns       : [n_agent][2 n_dir], entry 2j / 2j+1 = rollout of P + / - nu delta_j: the rewards of the steps taken
+ *   cost_trace    : NULL or [H][n_agent][2 n_dir]: cost of the state the reference appends to `states` at step t -- the
+ *                   state after the step, or the unchanged state where step t was refused (:149-152); NaN propagates
+ *                   as in np.max
+ *   cost_max      : NULL or [n_agent][2 n_dir]: the maximum of that over t (NaN if any is NaN; 0 for H = 0)
+ *   first_refused : NULL or [n_agent][2 n_dir]: the first refused step (H: none; always H for an ungated agent)
+ *   violations    : NULL or [n_agent][2 n_dir]: steps taken whose cost exceeded real_thresh, for ungated agents too
+ *   status        : NULL or [n_agent][2 n_dir]
+ * A gated agent whose simulator breaks the parameter rule (SW_ERR_PARAM's) gets SW_STATUS_PARAM in its status entries,
+ * NaN returns (and NaN cost_trace / cost_max entries), first_refused 0 and no violations; the other agents are
+ * unaffected.  Two kernel forms, chosen as sw_ars_rollouts_multi_f64 chooses (whole workgroups per agent, blockIdx.y =
+ * agent; surplus slots recompute the agent's last rollout and store nothing): n = 3 in the mirror-quad form of
+ * sw_safe_rollouts_f64 while SIMDs are idle, one rollout per lane otherwise and for every other n (there is no row
+ * form).  Per rollout each form runs the arithmetic of sw_safe_rollouts_f64 in the same form: returns, first_refused,
+ * violations and status of a gated agent have its bits, those of an ungated agent the bits of sw_rollout_f64.
+ * Errors, before any HIP call: a NULL policy / deltas / gated / sim / sim_thresh / real_thresh / returns: SW_ERR_NULL;
+ * n_agent < 1, n_agent > 65535, n_dir < 1, n_dir > 2^23, H < 0, an unknown cost_kind, a cost_index outside 0..d-1 with
+ * SW_COST_ABS_OBS, or 2^32 threads and more: SW_ERR_SIZE; parameters as everywhere. */
+int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64_t n_dir, int32_t H,
+                                   const double *policy, const double *deltas, double nu, const int32_t *gated,
+                                   const double *sim, const double *sim_thresh, const double *real_thresh,
+                                   int32_t cost_kind, int32_t cost_index, double *returns, double *cost_trace,
+                                   double *cost_max, int32_t *first_refused, int32_t *violations, int32_t *status,
+                                   void *stream);
 
 /* ---- CACLA (cacla/cacla_agent.py): whole training runs of many independent agents in ONE launch ----
  * An agent is n networks -- the n - 1 actors of ActorFA (one per torque), then the critic of CriticFA -- each a

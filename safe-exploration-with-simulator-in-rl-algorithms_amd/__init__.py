@@ -8,6 +8,7 @@ Public surface (mirrors the reference's module layout for this path):
     ars.SafeARSAgentBatch / ars.safe_exploration.run   ars/safe_exploration.py  (every safe agent of the sweep in one batch)
     ars.EnvParam / ars.ARSParam               ars/parameters.py
     safe_ars.Basic_ARS / safe_ars.Safe_ARS    safe_ars/ars.py  (batched one-step consumers of the step kernel)
+    safe_ars.ARSBatch / safe_ars.experiment   safe_ars/experiment.py  (all seeds, basic and safe, as one training batch)
     cacla.CACLA_agent / cacla.CACLABatch      cacla/cacla_agent.py  (whole training runs in one fused launch)
     cacla.swimmer_experiment                  cacla/swimmer_experiment.py  (the whole grid as one batch)
     cacla.CACLA_LQR_agent, cacla.cacla_safe_agent.*, cacla.CACLA_LQR_Batch

@@ -16,14 +16,15 @@ OBJ_DIR = LIB_PATH + ".obj"    # a library's objects live next to it: A/B builds
 # CACLA on the LQR problems (likewise)
 SOURCES = ["swimmer_kernels.hip", "swimmer_abi.hip", "swimmer_cacla.hip", "swimmer_lqr.hip", "direct_comm.cpp",
            "host_rng.cpp"]
-FAMILIES = ["swimmer_rollout_row.hip", "swimmer_rollout_n3.hip", "swimmer_rollout_lane.hip", "swimmer_step.hip",
-            "swimmer_cov.hip", "swimmer_update.hip"]
+FAMILIES = ["swimmer_rollout_row.hip", "swimmer_rollout_n3.hip", "swimmer_rollout_lane.hip",
+            "swimmer_rollout_safe_multi.hip", "swimmer_step.hip", "swimmer_cov.hip", "swimmer_update.hip"]
 HOST_ONLY = {"host_rng.cpp"}   # plain C++, no device pass: it picks its vector width from the CPU's features at
                                # run time (x86 builtins the device pass of a HIP compile refuses)
 HEADERS = ["rlglue_env.cpp", os.path.join("..", "..", "include", "rlglue_swimmer.h"),
            "swimmer_launch.h", "swimmer_cov.h", "swimmer_device.h", "swimmer_rollout_lane.inc",
            "swimmer_rollout_quad3.inc", "swimmer_rollout_oct3.inc", "swimmer_rollout_octp3.inc",
-           "swimmer_rollout_row.inc", "swimmer_rollout_multi.inc", "swimmer_update.inc", "swimmer_quad3.h",
+           "swimmer_rollout_row.inc", "swimmer_rollout_multi.inc", "swimmer_rollout_safe_oct3.inc",
+           "swimmer_rollout_safe_lane.inc", "swimmer_rollout_safe_multi.inc", "swimmer_update.inc", "swimmer_quad3.h",
            "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h",
            os.path.join("..", "..", "include", "swimmer_hip.h")] + FAMILIES
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + os.environ.get("SWIMMER_HIPCC_EXTRA", "").split()

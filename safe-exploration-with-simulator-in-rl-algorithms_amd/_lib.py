@@ -120,6 +120,11 @@ _PROTOTYPES = {
                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
                                                        ctypes.c_double, ctypes.c_int64, ctypes.c_void_p,
                                                        ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    # safe_ars/experiment.py: Basic_ARS / Safe_ARS rollouts of a batch of agents, the per-step gate in the kernel
+    "sw_safe_ars_rollouts_multi_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
+                                       + [ctypes.c_void_p] * 4 + [ctypes.c_int32, ctypes.c_int32]
+                                       + [ctypes.c_void_p] * 7),
     "sw_cacla_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
                          + [ctypes.c_void_p] * 9),
     "sw_lqr_cacla_run_f64": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 4

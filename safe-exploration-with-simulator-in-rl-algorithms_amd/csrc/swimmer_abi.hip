@@ -327,6 +327,36 @@ int sw_ars_rollouts_multi_counted_f64(const sw_params *p, int64_t n_agent, int64
     return launch_counted_lane(p, plan, n_agent, n_roll, H, a, nu, st);
 }
 
+// The exploration rollouts of a batch of Basic_ARS / Safe_ARS agents (safe_ars/experiment.py): the form and the grid
+// as sw_ars_rollouts_multi_f64 chooses them, with two forms to choose from -- mirror-quad where the plan says so
+// (n = 3), one rollout per lane everywhere else.  A cost trace counts as capture: the mirror-quad form addresses it
+// with 32-bit byte offsets, and the plan's test for a trajectory of 8 doubles per step covers its one.
+int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64_t n_dir, int32_t H,
+                                   const double *policy, const double *deltas, double nu, const int32_t *gated,
+                                   const double *sim, const double *sim_thresh, const double *real_thresh,
+                                   int32_t cost_kind, int32_t cost_index, double *returns, double *cost_trace,
+                                   double *cost_max, int32_t *first_refused, int32_t *violations, int32_t *status,
+                                   void *stream)
+{
+    int rc = check_params(real);
+    if (rc) return rc;
+    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;
+    if (n_agent > 65535 || n_dir > ((int64_t)1 << 23)) return SW_ERR_SIZE;
+    if (cost_kind != SW_COST_ABS_OBS && cost_kind != SW_COST_MAX_ABS_THETADOT) return SW_ERR_SIZE;
+    if (cost_kind == SW_COST_ABS_OBS && (cost_index < 0 || cost_index >= 2 * real->n + 2)) return SW_ERR_SIZE;
+    if (!policy || !deltas || !gated || !sim || !sim_thresh || !real_thresh || !returns) return SW_ERR_NULL;
+    const int64_t n_roll = 2 * n_dir;
+    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
+    RolloutPlan plan = plan_rollouts(real, slots, H, cost_trace != nullptr, /*allow_quad=*/false);
+    if (plan.form != Form::Oct3) plan = RolloutPlan{Form::Lane, form_block(Form::Lane), 0u, false};   // (no row form)
+    const dim3 grid = multi_grid(plan, n_agent, n_roll);
+    if ((int64_t)grid.x * grid.y * plan.block >= ((int64_t)1 << 32)) return SW_ERR_SIZE;   // threads of one launch
+    const SafeArsMultiArgs a{policy,  deltas,     gated,    sim,           sim_thresh, real_thresh,
+                             returns, cost_trace, cost_max, first_refused, violations, status};
+    SafeArsMultiLauncher *launch = plan.form == Form::Oct3 ? launch_safe_ars_multi_oct3 : launch_safe_ars_multi_lane;
+    return launch(real, plan, n_agent, n_roll, H, a, nu, cost_kind, cost_index, (hipStream_t)stream);
+}
+
 // ---- ARS iteration pipeline ---------------------------------------------------------
 // Host-side enqueue logic of one ARS iteration in native code: the caller's stream (the
 // critical path: rollouts -> [all-gather] -> update), a copy stream for the H2D of the deltas,

@@ -13,6 +13,7 @@
 #include "swimmer_rollout_row.hip"
 #include "swimmer_rollout_n3.hip"
 #include "swimmer_rollout_lane.hip"
+#include "swimmer_rollout_safe_multi.hip"
 #include "swimmer_step.hip"
 #include "swimmer_cov.hip"
 #include "swimmer_update.hip"

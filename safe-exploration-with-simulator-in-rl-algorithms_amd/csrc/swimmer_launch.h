@@ -48,6 +48,13 @@
 //                              agents.  The gate form takes every agent's simulator constants and threshold from device
 //                              arrays (the view derives C with sw::consts_of), the counted form every agent's number
 //                              of rollouts; both are the form's body behind swimmer_rollout_multi.inc
+//   swimmer_rollout_safe_multi.hip
+//   safe_ars_multi_oct3_kernel<COST,VIOL>, safe_ars_multi_lane_kernel<N>
+//                              sw_safe_ars_rollouts_multi_f64: the ARS exploration rollouts of MANY AGENTS with the
+//                              per-step simulator gate (Safe_ARS.rollout) or without it (Basic_ARS.rollout), agent by
+//                              agent: the safe-exploration bodies (swimmer_rollout_safe_oct3.inc, _lane.inc, shared with
+//                              safe_rollout_oct3_kernel / safe_rollout_kernel) behind swimmer_rollout_safe_multi.inc;
+//                              per step one cost value per rollout instead of a trajectory
 //   swimmer_update.hip
 //   ars_update_kernel          sigma_R, policy step, V2 statistics merge; pure latency between
 //                              two rollout launches: one round of loads, then LDS only
@@ -349,6 +356,33 @@ __device__ __forceinline__ bool sim_params_ok(double l, double m, double k)
     return l > 0.0 && m > 0.0 && isfinite(l) && isfinite(m) && isfinite(k);
 }
 
+// The state costs of the safe-exploration kernels (include/swimmer_hip.h SW_COST_*), one rollout per lane:
+// |obs[index]|, or max_i |thetadot_i| with np.max's NaN rule.
+template <int N>
+__device__ __forceinline__ double safe_cost(int32_t kind, int32_t index, double gdx, double gdy,
+                                            const double (&th)[N], const double (&thd)[N])
+{
+    if (kind == SW_COST_MAX_ABS_THETADOT) {
+        double c = fabs(thd[0]);
+#pragma unroll
+        for (int i = 1; i < N; ++i) c = fmax(c, fabs(thd[i]));   // np.max: NaN handled by the caller's <= test
+        bool nan = false;
+#pragma unroll
+        for (int i = 0; i < N; ++i) nan = nan || (thd[i] != thd[i]);
+        return nan ? __builtin_nan("") : c;                      // np.max propagates NaN, fmax would drop it
+    }
+    double v = (index == 0) ? gdx : gdy;                         // |obs[index]|, obs = [Gdx, Gdy, th_1, thd_1, ...]
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        v = (index == 2 + 2 * i) ? th[i] : v;
+        v = (index == 3 + 2 * i) ? thd[i] : v;
+    }
+    return fabs(v);
+}
+
+// mirror-quad safe-exploration kernels: a value committed where the gate is open
+__device__ __forceinline__ double oct_sel(bool take, double a, double b) { return take ? a : b; }
+
 // This lane's pre-combined policy row V_i = c12 (W_{i-1} - W_i), W = (P +- nu delta) diag(inv_std)
 // (ars_agent.py:141-142, environment.py:32-34; u_{-1} = u_{n-1} = 0: free ends), and
 // nbias = -V_i . mean.  cols[j]: the observation column of entry j (the quad kernel keeps its
@@ -526,5 +560,20 @@ using SafeLauncher = int(const sw_params *real, const sw_params *sim, const Roll
                          double real_thresh, double *returns, double *traj, int32_t *first_refused,
                          int32_t *violations, int32_t *status, hipStream_t stream);
 SafeLauncher launch_safe_oct3, launch_safe_row, launch_safe_lane;
+// Safe exploration for the ARS rollouts of n_agent agents (sw_safe_ars_rollouts_multi_f64): agent-major arrays as in
+// MultiArgs, plus per agent gated [n_agent], sim [n_agent][3], sim_thresh / real_thresh [n_agent]; cost_trace
+// [H][n_agent][2 n_dir]; cost_max / first_refused / violations / status [n_agent][2 n_dir] (null: not wanted).
+// There is a mirror-quad form (n = 3) and a lane form (every n).
+struct SafeArsMultiArgs {
+    const double *policy, *deltas;
+    const int32_t *gated;
+    const double *sim, *sim_thresh, *real_thresh;
+    double *returns, *cost_trace, *cost_max;
+    int32_t *first_refused, *violations, *status;
+};
+using SafeArsMultiLauncher = int(const sw_params *real, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll,
+                                 int32_t H, const SafeArsMultiArgs &a, double nu, int32_t cost_kind,
+                                 int32_t cost_index, hipStream_t stream);
+SafeArsMultiLauncher launch_safe_ars_multi_oct3, launch_safe_ars_multi_lane;
 
 }  // namespace sw_launch

@@ -102,28 +102,6 @@ ars_counted_lane_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_roll_max, int3
 // into the trajectory.  Costs (include/swimmer_hip.h SW_COST_*): |obs[j]|, or max_i |thetadot_i| (the reference's
 // own experiment, safe_ars/experiment.py:45).
 template <int N>
-__device__ __forceinline__ double safe_cost(int32_t kind, int32_t index, double gdx, double gdy,
-                                            const double (&th)[N], const double (&thd)[N])
-{
-    if (kind == SW_COST_MAX_ABS_THETADOT) {
-        double c = fabs(thd[0]);
-#pragma unroll
-        for (int i = 1; i < N; ++i) c = fmax(c, fabs(thd[i]));   // np.max: NaN handled by the caller's <= test
-        bool nan = false;
-#pragma unroll
-        for (int i = 0; i < N; ++i) nan = nan || (thd[i] != thd[i]);
-        return nan ? __builtin_nan("") : c;                      // np.max propagates NaN, fmax would drop it
-    }
-    double v = (index == 0) ? gdx : gdy;                         // |obs[index]|, obs = [Gdx, Gdy, th_1, thd_1, ...]
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        v = (index == 2 + 2 * i) ? th[i] : v;
-        v = (index == 3 + 2 * i) ? thd[i] : v;
-    }
-    return fabs(v);
-}
-
-template <int N>
 __global__ void __launch_bounds__(kRollBlock)
 safe_rollout_kernel(sw::Consts Creal, sw::Consts Csim, int64_t n_roll, int32_t H,
                     const double *__restrict__ policies, int32_t cost_kind, int32_t cost_index,
@@ -131,84 +109,9 @@ safe_rollout_kernel(sw::Consts Creal, sw::Consts Csim, int64_t n_roll, int32_t H
                     double *__restrict__ traj, int32_t *__restrict__ first_refused,
                     int32_t *__restrict__ violations, int32_t *__restrict__ status)
 {
-    constexpr int D = 2 * N + 2, M = N - 1;
-    const int64_t r = (int64_t)blockIdx.x * kRollBlock + threadIdx.x;
-    if (r >= n_roll) return;
-    double W[M][D];
-    const double *pl = policies + r * (M * D);
-#pragma unroll
-    for (int i = 0; i < M; ++i)
-#pragma unroll
-        for (int j = 0; j < D; ++j) W[i][j] = pl[i * D + j];
-    double gdx = 0.0, gdy = 0.0, th[N], thd[N];      // real_env.reset() (:133)
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        th[i] = kHalfPi;
-        thd[i] = 0.0;
-    }
-    auto record = [&](int32_t t) {
-        double *tp = traj + (int64_t)t * D * n_roll + r;
-        tp[0] = gdx;
-        tp[n_roll] = gdy;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            tp[(int64_t)(2 + 2 * i) * n_roll] = th[i];
-            tp[(int64_t)(3 + 2 * i) * n_roll] = thd[i];
-        }
-    };
-    double total = 0.0, thmax = 0.0;
-    bool ok = true;
-    int32_t refused_at = H, over = 0;
-    for (int32_t t = 0; t < H; ++t) {
-        thmax = sw::track_angle_range<N>(thmax, th);
-        double sm[D];
-        sm[0] = gdx;
-        sm[1] = gdy;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            sm[2 + 2 * i] = th[i];
-            sm[3 + 2 * i] = thd[i];
-        }
-        double u[M];                                  // ac = policy @ obs (:139)
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            double a0 = W[i][0] * sm[0], a1 = W[i][1] * sm[1];
-#pragma unroll
-            for (int j = 2; j < D; j += 2) {
-                a0 = __builtin_fma(W[i][j], sm[j], a0);
-                a1 = __builtin_fma(W[i][j + 1], sm[j + 1], a1);
-            }
-            u[i] = a0 + a1;
-        }
-        // the simulator's look-ahead from the real state (:120-121)
-        double sgx = gdx, sgy = gdy, sth[N], sthd[N], srew;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            sth[i] = th[i];
-            sthd[i] = thd[i];
-        }
-        (void)sw::euler_step<N>(Csim, sgx, sgy, sth, sthd, u, srew);
-        if (!(safe_cost<N>(cost_kind, cost_index, sgx, sgy, sth, sthd) <= sim_thresh)) {   // :122, NaN refuses
-            refused_at = t;
-            break;
-        }
-        double rew;
-        ok = sw::euler_step<N>(Creal, gdx, gdy, th, thd, u, rew) && ok;                     // :142
-        total += rew;
-        over += (safe_cost<N>(cost_kind, cost_index, gdx, gdy, th, thd) > real_thresh) ? 1 : 0;   // :143-144
-        if (traj) record(t);
-    }
-    if (traj)
-        for (int32_t t = refused_at; t < H; ++t) record(t);      // :151: the unchanged state, step after step
-    bool fin = isfinite(gdx) && isfinite(gdy);
-#pragma unroll
-    for (int i = 0; i < N; ++i) fin = fin && isfinite(th[i]) && isfinite(thd[i]);
-    const bool in_range = thmax < sw::kAngleLimit;
-    returns[r] = in_range ? total : __builtin_nan("");
-    if (first_refused) first_refused[r] = refused_at;
-    if (violations) violations[r] = over;
-    if (status)
-        status[r] = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) | (in_range ? 0 : SW_STATUS_RANGE);
+#define SW_SAFE_MULTI 0
+#include "swimmer_rollout_safe_lane.inc"
+#undef SW_SAFE_MULTI
 }
 
 }  // namespace

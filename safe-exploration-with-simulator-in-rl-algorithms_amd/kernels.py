@@ -562,6 +562,38 @@ def ars_update_multi_counted(p: SwParams, H: int, count, returns, deltas, policy
     return policy
 
 
+def safe_ars_rollouts_multi(p_real: SwParams, H: int, policy, deltas, nu: float, gated, sim, sim_thresh, real_thresh,
+                            cost_kind: int, cost_index: int, returns=None, cost_trace=None, cost_max=None,
+                            first_refused=None, violations=None, status=None):
+    """The exploration rollouts of A Basic_ARS / Safe_ARS agents in ONE launch (sw_safe_ars_rollouts_multi_f64):
+    policy [A, m, d], deltas [A, N, m, d], gated int32 [A] (0: every step is taken; else the per-step simulator gate),
+    sim [A, 3] = each agent's simulator (l_i, m_i, k), sim_thresh / real_thresh [A].  Returns `returns` [A, 2N]: row a
+    holds what safe_rollouts (gated) or rollout (ungated) gives for agent a's policies P + / - nu delta.  Optional
+    outputs, filled when given: cost_trace [H, A, 2N] (the cost of the state after step t, of the unchanged state where
+    the step was refused), cost_max [A, 2N], first_refused / violations / status int32 [A, 2N].  A gated agent whose
+    simulator breaks the parameter rule: SW_STATUS_PARAM, NaN returns, first_refused 0."""
+    require_gpu()
+    A, N, dev = _multi_shapes(p_real, policy, deltas, None, None)
+    _want_i32(gated, "gated", (A,), dev)
+    _want(sim, "sim", (A, 3))
+    _want(sim_thresh, "sim_thresh", (A,))
+    _want(real_thresh, "real_thresh", (A,))
+    if cost_trace is not None:
+        _want(cost_trace, "cost_trace", (H, A, 2 * N))
+    if cost_max is not None:
+        _want(cost_max, "cost_max", (A, 2 * N))
+    for name, t in (("first_refused", first_refused), ("violations", violations), ("status", status)):
+        if t is not None:
+            _want_i32(t, name, (A, 2 * N), dev)
+    returns = _f64((A, 2 * N), dev) if returns is None else _want(returns, "returns", (A, 2 * N))
+    check(load().sw_safe_ars_rollouts_multi_f64(ctypes.byref(p_real), A, N, H, ptr(policy), ptr(deltas), float(nu),
+                                                ptr(gated), ptr(sim), ptr(sim_thresh), ptr(real_thresh),
+                                                int(cost_kind), int(cost_index), ptr(returns), ptr(cost_trace),
+                                                ptr(cost_max), ptr(first_refused), ptr(violations), ptr(status),
+                                                stream_ptr()), "sw_safe_ars_rollouts_multi_f64")
+    return returns
+
+
 CACLA_HIDDEN = 12   # SW_CACLA_HIDDEN: the reference's hidden width (cacla_agent.py:165-166)
 
 

@@ -2,7 +2,8 @@
 path: a real swimmer (m, l, k) = (1, 1, 10), a simulator whose parameters are off by EPSILON in a random direction, the
 cost "maximum speed angle" max_i |thetadot_i| (:45), Basic_ARS and Safe_ARS trained from the same seed; prints both
 learning curves, the worst cost either agent ever reached in the real world, and how many rollouts the gate stopped.
-Plots, argparse and the seeds loop of the reference script are not reproduced (design aid).
+One seed, one agent at a time (design aid); the whole script -- seeds loop, flags, figure -- is swimmer_amd.safe_ars.experiment,
+which trains every agent of every seed as one batch.
     N=64 B=32 ITERS=60 H=500 THRESH=3.0 EPSILON=0.05 python scripts/safe_train_demo.py"""
 import os
 import sys
