@@ -35,6 +35,9 @@
  *                        state                                       ars/estimator.py:36-62
  *   sw_step_residual_pop_f64  Estimator.I for a whole CMA-ES generation in one launch (the objective of
  *                        Estimator.estimate_real_env_param's search)  ars/estimator.py:36-62, :89-110
+ *   sw_step_residual_sets_f64, sw_step_residual_normal_sets_f64
+ *                        the same search, and its least-squares refinement, for many estimators in lock-step: one
+ *                        launch per generation / per refinement request for all of them (ars/estimator_batch.py)
  *   sw_safe_rollouts_f64 Safe_ARS.isSafe + Safe_ARS.rollout (the one-step simulator look-ahead that gates
  *                        every real step)                            safe_ars/ars.py:111-153
  *   sw_safe_ars_rollouts_multi_f64
@@ -164,6 +167,51 @@ int64_t sw_step_residual_blocks(int64_t n_env);
 int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double *cand, int64_t n_env,
                              const double *state, const double *action, const double *next_ref, double *partial,
                              double *value, int32_t *cand_status, void *stream);
+
+/* sw_step_residual_pop_f64 for candidates that do not all score on the same transitions: a batch of estimators whose
+ * searches advance in lock-step, one launch per generation for all of them.
+ *   state, action, next_ref : the concatenated transitions of every set, SoA [d][n_env], [m][n_env], [d][n_env]
+ *   set_begin [n_set + 1]   : int64, on the device, ascending; set s is columns [set_begin[s], set_begin[s + 1]),
+ *                             every set has at least one transition
+ *   max_set_len             : the longest set (sizes the grid and the row stride of `partial`)
+ *   cand [n_cand][3]        : (l_i, m_i, k) per candidate; cand_set [n_cand]: int32, on the device, ascending (the
+ *                             candidates of a set are contiguous); a set may have no candidate
+ *   partial [n_cand][sw_step_residual_blocks(max_set_len)] : the first sw_step_residual_blocks(length of j's set)
+ *                             entries of row j have the bits sw_step_residual_f64 writes for candidate j on its set
+ *                             alone (256-transition blocks counted from the set's first column); the rest of the row
+ *                             is not written
+ *   value [n_cand] (may be NULL) : the written entries of row j summed in sw_step_residual_pop_f64's order
+ *   cand_status [n_cand] (may be NULL) : SW_STATUS_PARAM (NaN partials and value) or 0, per candidate
+ * A candidate whose set index or bounds do not fit (index outside [0, n_set), columns outside [0, n_env), empty, or
+ * longer than max_set_len) is not scored: nothing is read or written for it but its status.
+ * Errors, before any HIP call: NULL pointer SW_ERR_NULL; n_set < 1, n_cand < 1, n_cand > 524280, max_set_len < 1,
+ * n_env < 1 or max_set_len > n_env SW_ERR_SIZE; twin model SW_ERR_PARAM. */
+int sw_step_residual_sets_f64(const sw_params *base, int64_t n_set, const int64_t *set_begin, int64_t max_set_len,
+                              int64_t n_cand, const double *cand, const int32_t *cand_set, int64_t n_env,
+                              const double *state, const double *action, const double *next_ref, double *partial,
+                              double *value, int32_t *cand_status, void *stream);
+
+/* The normal equations of the estimator's least-squares refinement, per transition set, fused: every transition of set
+ * s is stepped at n_point parameter points, points [n_set][n_point][3] = (l_i, m_i, k), and the residual vectors r =
+ * step - next_ref (d components) are reduced without reaching memory.
+ *   n_point = 1 : out [n_set][1]  = r.r
+ *   n_point = 7 : points in the order centre, +e0, -e0, +e1, -e1, +e2, -e2; J_i = (r_{+i} - r_{-i}) inv_2e[s][i]
+ *                 (inv_2e [n_set][3]); out [n_set][13] = r.r | J^T J (9, row-major, symmetric in its bits) | J^T r (3),
+ *                 r at the centre
+ *   partial [n_set][1 or 13][sw_step_residual_blocks(max_set_len)] : scratch, the per-workgroup sums
+ *   active [n_set] (int32, may be NULL) : a set with active[s] == 0 is neither read nor written
+ *   set_status [n_set] (may be NULL)    : SW_STATUS_PARAM (NaN sums) when a point of the set breaks the parameter rule
+ * Sums go in a fixed order (per transition an FMA chain over the d components; per workgroup the lane tree and wave
+ * order of sw_step_residual_f64; per set the order of sw_step_residual_pop_f64's value): bit-reproducible.  A
+ * transition with an angle out of range makes its set's sums NaN.  set_begin, max_set_len and the transitions as in
+ * sw_step_residual_sets_f64; a set whose bounds do not fit is skipped.
+ * Errors, before any HIP call: NULL pointer SW_ERR_NULL (inv_2e only with 7 points); n_set < 1, n_set > 65535,
+ * max_set_len < 1, n_env < 1 or max_set_len > n_env SW_ERR_SIZE; twin model or n_point outside {1, 7} SW_ERR_PARAM. */
+int sw_step_residual_normal_sets_f64(const sw_params *base, int64_t n_set, const int64_t *set_begin,
+                                     int64_t max_set_len, int32_t n_point, const double *points, const double *inv_2e,
+                                     const int32_t *active, int64_t n_env, const double *state, const double *action,
+                                     const double *next_ref, double *partial, double *out, int32_t *set_status,
+                                     void *stream);
 
 int sw_accel_f64(const sw_params *p, int64_t n_env, const double *state,
                  const double *action, double *gdd, double *tdd, void *stream);

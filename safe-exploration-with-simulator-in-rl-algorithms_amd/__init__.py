@@ -6,6 +6,7 @@ Public surface (mirrors the reference's module layout for this path):
     ars.ARSAgent                              ars/ars_agent.py
     ars.Experiment                            ars/experiment.py  (its seeds train as one ars.ARSAgentBatch)
     ars.SafeARSAgentBatch / ars.safe_exploration.run   ars/safe_exploration.py  (every safe agent of the sweep in one batch)
+    ars.EstimatorBatch                        ars/estimator.py  (many simulator estimates in lock-step, one launch per generation)
     ars.EnvParam / ars.ARSParam               ars/parameters.py
     safe_ars.Basic_ARS / safe_ars.Safe_ARS    safe_ars/ars.py  (batched one-step consumers of the step kernel)
     safe_ars.ARSBatch / safe_ars.experiment   safe_ars/experiment.py  (all seeds, basic and safe, as one training batch)
@@ -21,10 +22,10 @@ Public surface (mirrors the reference's module layout for this path):
 from . import _build, _lib, kernels  # noqa: F401
 from ._lib import SwParams, SwimmerHipError  # noqa: F401
 from .envs import SwimmerEnv, VecSwimmerEnv  # noqa: F401
-from .ars import (ARSAgent, ARSAgentBatch, ARSParam, EnvParam, Environment, Experiment,  # noqa: F401
+from .ars import (ARSAgent, ARSAgentBatch, ARSParam, EnvParam, Environment, EstimatorBatch, Experiment,  # noqa: F401
                   SafeARSAgentBatch)
 from . import safe_ars  # noqa: F401
 from . import cacla  # noqa: F401
 
 __all__ = ["SwParams", "SwimmerHipError", "SwimmerEnv", "VecSwimmerEnv", "ARSAgent", "ARSAgentBatch", "SafeARSAgentBatch", "ARSParam",
-           "EnvParam", "Environment", "Experiment", "kernels"]
+           "EnvParam", "Environment", "EstimatorBatch", "Experiment", "kernels"]

@@ -78,6 +78,13 @@ _PROTOTYPES = {
     "sw_step_residual_blocks": (ctypes.c_int64, [ctypes.c_int64]),
     "sw_step_residual_pop_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
                                  + [ctypes.c_void_p] * 7),
+    "sw_step_residual_sets_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+                                  + [ctypes.c_void_p] * 7),
+    "sw_step_residual_normal_sets_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+                                         + [ctypes.c_void_p] * 7),
     "sw_accel_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
     "sw_rollout_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32]
                        + [ctypes.c_void_p] * 10),

@@ -152,17 +152,56 @@ def minimize(fun_population, x0, sigma0=1.0, popsize=None, seed=0, feasible=None
     return es
 
 
-def refine_least_squares(cost, normal, u0, feasible=None, max_iter=50):
-    """Levenberg-Marquardt on a zero-residual least-squares problem, from u0: cost(u) = r(u).r(u), normal(u) =
-    (J^T J, J^T r) at u.  A step is taken only when it lowers the cost, so the result is never worse than u0.  The
-    estimator runs it on the best point of the CMA-ES: I(x) is a sum of norms whose minimum lies at the end of a long,
-    curved, nearly flat valley (k / m is far less determined by the stored transitions than k l / m and m l^2), where
-    the CMA-ES stopping rules fire long before the minimum; in the model's own constants the valley is straight and
-    Gauss-Newton steps reach the minimum in a few iterations."""
+def minimize_many(fun_many, x0s, sigma0=1.0, popsize=None, seeds=None, feasibles=None, max_generations=None,
+                  tolfun=TOLFUN, tolx=TOLX):
+    """`minimize` for many independent searches in lock-step: one CMAES object per row of x0s, each with its own
+    generator (seeds[i]; default 0 for every instance).  Per generation every live instance asks, `fun_many(idx, Xs)`
+    is called ONCE -- idx the indices of the live instances, Xs[j] the points of instance idx[j] that its `feasible`
+    rule accepts (an empty array when it accepts none; the refused ones score +inf as in `minimize`) -> one array of
+    values per entry of Xs -- and every live instance is told.  An instance that stops drops out; the loop ends when
+    none is live.  sigma0, popsize, feasibles and max_generations are one value for all or a list with one per
+    instance.  Returns the list of CMAES objects; instance i ends exactly where minimize(fun_i, x0s[i], seed=seeds[i],
+    ...) ends."""
+    n = len(x0s)
+
+    def per(v, kind):
+        return list(v) if isinstance(v, kind) else [v] * n
+
+    sigma0, popsize = per(sigma0, (list, tuple, np.ndarray)), per(popsize, (list, tuple, np.ndarray))
+    feasibles, max_generations = per(feasibles, (list, tuple)), per(max_generations, (list, tuple, np.ndarray))
+    seeds = [0] * n if seeds is None else list(seeds)
+    if not all(len(v) == n for v in (sigma0, popsize, feasibles, max_generations, seeds)):
+        raise ValueError(f"expected one value or {n} values per argument")
+    es = [CMAES(x0s[i], sigma0[i], popsize=popsize[i], seed=seeds[i], feasible=feasibles[i],
+                max_generations=max_generations[i], tolfun=tolfun, tolx=tolx) for i in range(n)]
+    live = [i for i in range(n) if es[i].stop() is None]
+    while live:
+        Xs, oks = [], []
+        for i in live:
+            X = es[i].ask()
+            ok = (np.ones(es[i].lam, dtype=bool) if feasibles[i] is None
+                  else np.array([bool(feasibles[i](x)) for x in X]))
+            Xs.append(X)
+            oks.append(ok)
+        fs = fun_many(list(live), [X[ok] for X, ok in zip(Xs, oks)])
+        if len(fs) != len(live):
+            raise ValueError(f"fun_many returned {len(fs)} value arrays for {len(live)} instances")
+        for i, X, ok, fi in zip(live, Xs, oks, fs):
+            f = np.full(es[i].lam, np.inf)
+            if ok.any():
+                f[ok] = np.asarray(fi, dtype=np.float64).ravel()
+            es[i].tell(X, f)
+        live = [i for i in live if es[i].stop() is None]
+    return es
+
+
+def _refine_steps(u0, feasible, max_iter):
+    """refine_least_squares as a generator of requests: yields ("cost", u) and expects r(u).r(u) sent back, yields
+    ("normal", u) and expects (J^T J, J^T r); returns the refined point."""
     u = np.array(u0, dtype=np.float64)
-    c, mu = float(cost(u)), 1e-3
+    c, mu = float((yield "cost", u)), 1e-3
     for _ in range(max_iter):
-        G, g = normal(u)
+        G, g = yield "normal", u
         G, g = np.asarray(G, dtype=np.float64), np.asarray(g, dtype=np.float64)
         s = np.sqrt(np.diag(G))
         if not (np.all(np.isfinite(G)) and np.all(np.isfinite(g)) and np.all(s > 0)):
@@ -171,7 +210,7 @@ def refine_least_squares(cost, normal, u0, feasible=None, max_iter=50):
         while True:
             du = np.linalg.solve(Gs + mu * np.eye(u.size), -gs) / s
             un = u + du
-            cn = float(cost(un)) if (feasible is None or feasible(un)) else math.inf
+            cn = float((yield "cost", un)) if (feasible is None or feasible(un)) else math.inf
             if cn < c:
                 break
             mu *= 10.0
@@ -181,6 +220,56 @@ def refine_least_squares(cost, normal, u0, feasible=None, max_iter=50):
         if np.abs(du).max() <= 1e-14 * max(1.0, np.abs(u).max()) or c == 0.0:
             break
     return u
+
+
+def refine_least_squares(cost, normal, u0, feasible=None, max_iter=50):
+    """Levenberg-Marquardt on a zero-residual least-squares problem, from u0: cost(u) = r(u).r(u), normal(u) =
+    (J^T J, J^T r) at u.  A step is taken only when it lowers the cost, so the result is never worse than u0.  The
+    estimator runs it on the best point of the CMA-ES: I(x) is a sum of norms whose minimum lies at the end of a long,
+    curved, nearly flat valley (k / m is far less determined by the stored transitions than k l / m and m l^2), where
+    the CMA-ES stopping rules fire long before the minimum; in the model's own constants the valley is straight and
+    Gauss-Newton steps reach the minimum in a few iterations."""
+    steps = _refine_steps(u0, feasible, max_iter)
+    try:
+        kind, u = next(steps)
+        while True:
+            kind, u = steps.send(cost(u) if kind == "cost" else normal(u))
+    except StopIteration as done:
+        return done.value
+
+
+def refine_least_squares_many(cost_many, normal_many, U0, feasible=None, max_iter=50):
+    """refine_least_squares for many independent problems in lock-step.  Every instance runs the same steps as the
+    single function; per round all pending requests for normal equations are served by ONE call normal_many(idx, U)
+    -> [(J^T J, J^T r) per entry] and all pending cost requests by ONE call cost_many(idx, U) -> [r.r per entry] (idx
+    the instances' indices, U [len(idx), N] their points).  `feasible` is one rule for all or a list of one per
+    instance.  Returns the list of refined points: instance i's iterates are those of refine_least_squares given the
+    same callback values."""
+    n = len(U0)
+    feasible = list(feasible) if isinstance(feasible, (list, tuple)) else [feasible] * n
+    steps = [_refine_steps(U0[i], feasible[i], max_iter) for i in range(n)]
+    result, pending = [None] * n, {}
+
+    def advance(i, value=None, first=False):
+        try:
+            pending[i] = next(steps[i]) if first else steps[i].send(value)
+        except StopIteration as done:
+            pending.pop(i, None)
+            result[i] = done.value
+
+    for i in range(n):
+        advance(i, first=True)
+    while pending:
+        for kind, serve in (("normal", normal_many), ("cost", cost_many)):
+            idx = [i for i in sorted(pending) if pending[i][0] == kind]
+            if not idx:
+                continue
+            values = serve(idx, np.stack([pending[i][1] for i in idx]))
+            if len(values) != len(idx):
+                raise ValueError(f"{kind}_many returned {len(values)} values for {len(idx)} instances")
+            for i, v in zip(idx, values):
+                advance(i, v)
+    return result
 
 
 def to_constants(m_i, l_i, k):

@@ -29,7 +29,9 @@ from .parameters import EnvParam
 class Estimator(object):
 
     def __init__(self, database, guess_param, capacity, unknowns=('m_i', 'l_i', 'k'),
-                 device="cuda:0"):
+                 device="cuda:0", subset=None):
+        """subset: the rollouts to estimate from, instead of `capacity` draws from NumPy's global generator (which
+        is then not touched; EstimatorBatch draws its estimators' subsets from generators of their own)."""
         assert database.size > 0, "Database is empty"
         if database._device_batches and not database._trajectories:   # still on the GPU: keep it there
             assert database._device_batches[0][0].shape[0] == guess_param.H, "Rollouts are not the same"
@@ -38,7 +40,8 @@ class Estimator(object):
         self.guess_param = guess_param
         self.unknowns = unknowns
         self.database = database
-        self.subset = np.random.randint(0, self.database.size, capacity)   # estimator.py:33
+        self.subset = (np.random.randint(0, self.database.size, capacity) if subset is None   # estimator.py:33
+                       else np.asarray(subset, dtype=np.int64))
         self.iter = 0
         self.device = torch.device(device)
         self._cache = None

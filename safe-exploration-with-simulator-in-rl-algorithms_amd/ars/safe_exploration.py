@@ -15,6 +15,11 @@ The simulators: in the reference every actor perturbs its own copy of the real p
 started process's generator; here they are approximate_env_params(..., approx_error=epsilon) draws from `rng`, taken
 in the order of the loops (A, then epsilon, then seed).
 
+With a `guess_param` the simulators are COMPUTED instead (the reference's ARSAgent(guess_param=...) route, ars/ars_agent.py:
+40-44): the hand controller's rollouts are stored, and every agent's simulator is the estimate of one estimator on that
+store -- capacity 1, the agent's seed draws its rollout and seeds its search -- all of them as ONE EstimatorBatch, one
+launch per CMA-ES generation for the whole sweep.
+
 run() returns the numbers the reference plots and writes its four figures (one per A) when matplotlib imports.
 Every size is an argument; the defaults are the reference's.
 """
@@ -23,6 +28,8 @@ import os
 import numpy as np
 
 from .ars_agent import approximate_env_params
+from .database import Database
+from .estimator_batch import EstimatorBatch
 from .experiment import Experiment
 from .parameters import ARSParam, EnvParam, Threshold
 from .safe_agent_batch import SafeARSAgentBatch
@@ -48,11 +55,16 @@ def sweep_agents(l, H, A_values, epsilons, n_seed, K, B, rng=None):
 
 
 def run(*, A_values=(0.1, 0.3, 0.5, 0.7), epsilons=None, n_seed=8, n_iter=400, hand_iter=200, H=1000, K=1, B=0.001,
-        N=1, b=1, alpha=0.0075, nu=0.01, results_path="results/", data_path="ars/data/", rng=None, device=None):
+        N=1, b=1, alpha=0.0075, nu=0.01, results_path="results/", data_path="ars/data/", rng=None, device=None,
+        guess_param=None, estimator_options=None):
     """The whole script.  Returns a dict: l, epsilons, A_values, and per A (lists in the order of A_values)
-    min_return [n_eps], max_mean_returns [n_eps], sim_thresh_range [n_eps]; r_graphs [A][eps][seed][n_iter + 1].
+    min_return [n_eps], max_mean_returns [n_eps], sim_thresh_range [n_eps]; r_graphs [A][eps][seed][n_iter + 1];
+    sim_params, the agents' simulators in batch order.
     Files: data_path + saved_hand_policy.npy and threshold.txt, the hand controller's Experiment files under
-    results_path, and results_path + epsilon_sim_threshold_H=.._K=.._A=.._B=...png per A."""
+    results_path, and results_path + epsilon_sim_threshold_H=.._K=.._A=.._B=...png per A.
+    guess_param (an EnvParam with the real world's n, h and H): estimate every agent's simulator from the hand
+    controller's stored rollouts (data_path + hand_trajectories.npz) with one EstimatorBatch, starting at the guess;
+    estimator_options are passed to EstimatorBatch.estimate."""
     epsilons = np.linspace(0.0001, 0.01, 10) if epsilons is None else np.asarray(epsilons, dtype=np.float64)
     A_values = list(A_values)
     results_path, data_path = os.path.join(results_path, ""), os.path.join(data_path, "")   # Experiment appends to it
@@ -64,8 +76,9 @@ def run(*, A_values=(0.1, 0.3, 0.5, 0.7), epsilons=None, n_seed=8, n_iter=400, h
     hand_agent = ARSParam('HandControl', V1=True, n_iter=hand_iter, H=H, N=N, b=b, alpha=alpha, nu=nu, safe=False,
                           threshold=0, initial_w='Zero')
     policy_path = os.path.join(data_path, "saved_hand_policy")
-    returns = Experiment(ep, results_path=results_path, save_policy_path=policy_path).plot(n_seed=1,
-                                                                                           agent_param=hand_agent)
+    store_path = os.path.join(data_path, "hand_trajectories.npz") if guess_param is not None else None
+    returns = Experiment(ep, results_path=results_path, save_data_path=store_path,
+                         save_policy_path=policy_path).plot(n_seed=1, agent_param=hand_agent)
     # the safety threshold from the known controller (:39-42)
     l = float(np.mean(returns, axis=0)[-1] * 0.99)
     print(f"\nSafety threshold: {l}")
@@ -73,12 +86,17 @@ def run(*, A_values=(0.1, 0.3, 0.5, 0.7), epsilons=None, n_seed=8, n_iter=400, h
 
     # every safe agent of the sweep in one batch (:54-82)
     seeds, sims, sim_thresholds, ranges = sweep_agents(l, H, A_values, epsilons, n_seed, K, B, rng)
+    if guess_param is not None:   # computed simulators: one estimator per agent, all searches in lock-step
+        store = Database()
+        store.load(store_path)
+        sims = EstimatorBatch(store, guess_param, capacity=1, seeds=seeds,
+                              device=device or "cuda:0").estimate(**(estimator_options or {}))
     real_agent = ARSParam('RLControl', V1=True, n_iter=n_iter, H=H, N=N, b=b, alpha=alpha, nu=nu, safe=True,
                           threshold=l, initial_w=policy_path + ".npy")
     batch = SafeARSAgentBatch(ep, real_agent, seeds, sims, sim_thresholds, device=device)
     curves = batch.runTraining()
     r_graphs = curves.reshape(len(A_values), len(epsilons), n_seed, n_iter + 1)
-    out = dict(l=l, epsilons=epsilons, A_values=A_values, r_graphs=r_graphs, sim_thresh_range=ranges,
+    out = dict(l=l, epsilons=epsilons, A_values=A_values, r_graphs=r_graphs, sim_thresh_range=ranges, sim_params=sims,
                min_return=[], max_mean_returns=[], violations=batch.violations.reshape(r_graphs.shape[:3]))
     for g in r_graphs:
         out["min_return"].append(np.array([np.nanmin(r) for r in g]))                       # :80

@@ -15,6 +15,13 @@
 //                              (4.87 vs 5.62 TB/s: 90 VGPRs, fewer loads in flight) and was dropped.
 //   accel_kernel<N,TWIN>       accelerations only
 //   step_residual*_kernel      the estimator's objective, one parameter set or a population
+//   step_residual_sets_kernel<N>  the population objective for MANY ESTIMATORS in one launch (sw_step_residual_sets_f64):
+//                              candidate j scores on transition set cand_set[j]; blocks are counted from the set's
+//                              first column, so every partial has step_residual_kernel's bits on the set alone
+//   step_residual_normal_sets_kernel<N,NP>  the least-squares refinement's r.r (NP = 1) or r.r | J^T J | J^T r (NP = 7,
+//                              central differences in registers) per transition set, fixed-order sums
+//                              (sw_step_residual_normal_sets_f64); residual_set_rows_sum_kernel adds both kernels'
+//                              per-block rows in residual_rows_sum_kernel's order
 //   env1_kernel                one swimmer handed over in host memory (sw_env1)
 //   swimmer_rollout_n3.hip
 //   rollout_oct3_kernel        n = 3, H steps in one launch, one segment per lane WITH LANE ROLES: two
@@ -233,6 +240,7 @@ constexpr int kMomBlock = 256;        // standalone covariance pass: threads per
 constexpr int64_t kStepStreamBytes = (int64_t)256 << 20;   // beyond the Infinity Cache: nontemporal accesses
 constexpr int kPopGroup = 8;          // sw_step_residual_pop_f64: candidates per workgroup, ...
 constexpr int64_t kPopMaxCandidates = (int64_t)65535 * kPopGroup;   // ... and at most 65535 groups (grid.y)
+constexpr int64_t kSetsMax = 65535;   // sw_step_residual_normal_sets_f64: one grid row (grid.y) per transition set
 constexpr double kHalfPi = 1.57079632679489661923;  // math.pi / 2 (remy_swimmer_env.py:65)
 constexpr double kTwinStart = 0.001;                // SwimmerEnvironment.cpp:41
 

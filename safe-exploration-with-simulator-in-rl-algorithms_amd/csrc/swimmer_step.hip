@@ -1,5 +1,5 @@
 // swimmer_step.hip -- one physics step for a batch of environments: step / accelerations / reset, the estimator's
-// residual kernels (one parameter set or a population), the batch-1 environment (sw_env1), and their entry points.
+// residual kernels (one parameter set, a population, or populations over many transition sets), the batch-1 environment (sw_env1), and their entry points.
 #include <cstring>
 #include <new>
 
@@ -222,6 +222,297 @@ residual_rows_sum_kernel(int64_t nb, const double *__restrict__ partial, double 
     if (threadIdx.x == 0) value[blockIdx.x] = t;
 }
 
+// Columns [b0, b0 + len) of set s of the concatenated transitions (set_begin [n_set + 1], ascending).  False for a set
+// index or bounds that do not fit the arrays the host sized (n_set, n_env, the row stride from max_set_len): such a
+// set is never read and nothing is written for it.
+__device__ __forceinline__ bool set_span(const int64_t *__restrict__ set_begin, int64_t s, int64_t n_set, int64_t n_env,
+                                         int64_t max_set_len, int64_t &b0, int64_t &len)
+{
+    b0 = len = 0;
+    if (s < 0 || s >= n_set) return false;
+    const int64_t a = set_begin[s], b = set_begin[s + 1];
+    if (a < 0 || b > n_env || b <= a || b - a > max_set_len) return false;
+    b0 = a;
+    len = b - a;
+    return true;
+}
+
+// step_residual_pop_kernel for candidates that do not all score on the same transitions (a batch of estimators in
+// lock-step): candidate j scores on set cand_set[j] of the concatenated transitions.  blockIdx.x counts 256-transition
+// blocks FROM THE SET'S FIRST COLUMN, so per candidate everything is step_residual_kernel's on the set alone: partition,
+// consts, euler_step, FMA chain, lane tree, wave order.  A workgroup reads its transitions once for each run of
+// same-set candidates of its group (cand_set ascending: one run per set); a run whose set ends before this block is
+// skipped, and a workgroup beyond the longest set of its group returns before the first barrier (both tests are
+// workgroup-uniform).  partial is [n_cand][gridDim.x]; row j's entries beyond its set's last block are not written.
+template <int N>
+__global__ void __launch_bounds__(kStepBlock)
+step_residual_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *__restrict__ set_begin, int64_t max_set_len,
+                          int64_t n_cand, const double *__restrict__ cand, const int32_t *__restrict__ cand_set,
+                          int64_t n_env, const double *__restrict__ sin_, const double *__restrict__ act,
+                          const double *__restrict__ next_ref, double *__restrict__ partial,
+                          int32_t *__restrict__ cand_status)
+{
+    constexpr int M = N - 1;
+    __shared__ sw::Consts cc[kPopGroup];
+    __shared__ int cok[kPopGroup];
+    __shared__ int64_t cbeg[kPopGroup], clen[kPopGroup];
+    __shared__ int32_t cset[kPopGroup];
+    __shared__ double wsum[kPopGroup][kStepBlock / kWave];
+    const int64_t j0 = (int64_t)blockIdx.y * kPopGroup;
+    const int nc = (int)(n_cand - j0 < kPopGroup ? n_cand - j0 : kPopGroup);
+    const int64_t t0 = (int64_t)blockIdx.x * kStepBlock;   // this block's first transition, counted inside a set
+    int64_t longest = 0;
+    for (int c = 0; c < nc; ++c) {   // uniform
+        int64_t b0, len;
+        (void)set_span(set_begin, cand_set[j0 + c], n_set, n_env, max_set_len, b0, len);
+        longest = len > longest ? len : longest;
+    }
+    if ((int)threadIdx.x < nc) {
+        const double *x = cand + (j0 + threadIdx.x) * 3;   // [l_i, m_i, k]
+        const double l = x[0], m = x[1], k = x[2];
+        const bool ok = sim_params_ok(l, m, k);
+        if (cand_status && blockIdx.x == 0) cand_status[j0 + threadIdx.x] = ok ? SW_STATUS_OK : SW_STATUS_PARAM;
+        if (t0 < longest) {
+            int64_t b0, len;
+            const int32_t s = cand_set[j0 + threadIdx.x];
+            (void)set_span(set_begin, s, n_set, n_env, max_set_len, b0, len);
+            cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
+            cok[threadIdx.x] = ok;
+            cset[threadIdx.x] = s;
+            cbeg[threadIdx.x] = b0;
+            clen[threadIdx.x] = len;
+        }
+    }
+    if (t0 >= longest) return;   // beyond every set of this group (uniform, in front of the barriers)
+    __syncthreads();
+    int c = 0;
+    while (c < nc) {             // one trip per run of same-set candidates (uniform)
+        int c1 = c + 1;
+        while (c1 < nc && cset[c1] == cset[c]) ++c1;
+        const int64_t b0 = cbeg[c], len = clen[c];
+        if (t0 < len) {
+            const bool live = t0 + threadIdx.x < len;
+            const int64_t e = b0 + t0 + threadIdx.x;
+            double gdx = 0.0, gdy = 0.0, th[N], thd[N], u[M], rx = 0.0, ry = 0.0, rth[N], rthd[N];
+#pragma unroll
+            for (int i = 0; i < N; ++i) th[i] = thd[i] = rth[i] = rthd[i] = 0.0;
+#pragma unroll
+            for (int i = 0; i < M; ++i) u[i] = 0.0;
+            if (live) {
+                gdx = sin_[e];
+                gdy = sin_[n_env + e];
+#pragma unroll
+                for (int i = 0; i < N; ++i) {
+                    th[i] = sin_[(int64_t)(2 + 2 * i) * n_env + e];
+                    thd[i] = sin_[(int64_t)(3 + 2 * i) * n_env + e];
+                }
+#pragma unroll
+                for (int i = 0; i < M; ++i) u[i] = act[(int64_t)i * n_env + e];
+                rx = next_ref[e];
+                ry = next_ref[n_env + e];
+#pragma unroll
+                for (int i = 0; i < N; ++i) {
+                    rth[i] = next_ref[(int64_t)(2 + 2 * i) * n_env + e];
+                    rthd[i] = next_ref[(int64_t)(3 + 2 * i) * n_env + e];
+                }
+            }
+            const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+#pragma unroll 1
+            for (int k = c; k < c1; ++k) {
+                double dist = 0.0;
+                if (live) {
+                    double x = gdx, y = gdy, t[N], td[N], r;
+#pragma unroll
+                    for (int i = 0; i < N; ++i) {
+                        t[i] = th[i];
+                        td[i] = thd[i];
+                    }
+                    (void)sw::euler_step<N>(cc[k], x, y, t, td, u, r);
+                    double q = (x - rx) * (x - rx);
+                    q = __builtin_fma(y - ry, y - ry, q);
+#pragma unroll
+                    for (int i = 0; i < N; ++i) {
+                        q = __builtin_fma(t[i] - rth[i], t[i] - rth[i], q);
+                        q = __builtin_fma(td[i] - rthd[i], td[i] - rthd[i], q);
+                    }
+                    dist = (in_range && cok[k]) ? sqrt(q) : __builtin_nan("");
+                }
+#pragma unroll
+                for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
+                if (threadIdx.x % kWave == 0) wsum[k][threadIdx.x / kWave] = dist;
+            }
+        }
+        c = c1;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nc && t0 < clen[threadIdx.x]) {
+        double t = wsum[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
+        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// residual_rows_sum_kernel for rows of different lengths: row r of partial [gridDim.x][stride] belongs to set
+// row_set[r] (nullptr: to set r / rows_per_set) and holds one entry per 256-transition block of that set; value[r] =
+// their sum in residual_rows_sum_kernel's order.  A set with active[s] == 0, or with bounds that do not fit, is skipped.
+__global__ void __launch_bounds__(kWave)
+residual_set_rows_sum_kernel(int64_t n_set, const int64_t *__restrict__ set_begin, int64_t max_set_len, int64_t n_env,
+                             const int32_t *__restrict__ row_set, int rows_per_set, const int32_t *__restrict__ active,
+                             int64_t stride, const double *__restrict__ partial, double *__restrict__ value)
+{
+    const int64_t s = row_set ? (int64_t)row_set[blockIdx.x] : (int64_t)(blockIdx.x / rows_per_set);
+    int64_t b0, len;
+    if (!set_span(set_begin, s, n_set, n_env, max_set_len, b0, len)) return;
+    if (active && !active[s]) return;
+    const int64_t nb = (len + kStepBlock - 1) / kStepBlock;
+    const double *row = partial + (int64_t)blockIdx.x * stride;
+    double t = 0.0;
+    for (int64_t b = threadIdx.x; b < nb; b += kWave) t += row[b];
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) t += __shfl_down(t, off, kWave);
+    if (threadIdx.x == 0) value[blockIdx.x] = t;
+}
+
+// The least-squares refinement's normal equations for many transition sets at once (Estimator._residual_normal /
+// _residual_cost for a batch of estimators): workgroup (b, s) steps block b of set s at NP parameter points
+// (points [n_set][NP][3] = l_i, m_i, k; NP = 7: centre, +e0, -e0, +e1, -e1, +e2, -e2), forms the residual vectors r =
+// step - next_ref in registers and, with 7 points, the central-difference columns J_i = (r_+i - r_-i) inv_2e[s][i],
+// and sums K = 1 (r.r) or 13 (r.r | J^T J row-major | J^T r) values over its transitions in a fixed order: FMA chain
+// over the d components, lanes by shuffle tree, the four waves in order.  partial [n_set][K][gridDim.x]; the simulated
+// states never reach memory.  Out-of-range angles, or a point that breaks the parameter rule, make the sums NaN.
+template <int N, int NP>
+__global__ void __launch_bounds__(kStepBlock)
+step_residual_normal_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *__restrict__ set_begin,
+                                 int64_t max_set_len, const double *__restrict__ points,
+                                 const double *__restrict__ inv_2e, const int32_t *__restrict__ active, int64_t n_env,
+                                 const double *__restrict__ sin_, const double *__restrict__ act,
+                                 const double *__restrict__ next_ref, double *__restrict__ partial,
+                                 int32_t *__restrict__ set_status)
+{
+    constexpr int M = N - 1, D = 2 * N + 2, K = NP == 7 ? 13 : 1;
+    static_assert(NP == 1 || NP == 7, "one point (cost) or seven (normal equations)");
+    __shared__ sw::Consts cc[NP];
+    __shared__ int cok[NP];
+    __shared__ double wsum[K][kStepBlock / kWave];
+    const int64_t s = blockIdx.y, t0 = (int64_t)blockIdx.x * kStepBlock;
+    int64_t b0, len;
+    if (!set_span(set_begin, s, n_set, n_env, max_set_len, b0, len)) return;   // uniform, in front of the barriers
+    if (active && !active[s]) return;
+    if (t0 >= len) return;
+    if ((int)threadIdx.x < NP) {
+        const double *x = points + (s * NP + threadIdx.x) * 3;
+        const double l = x[0], m = x[1], k = x[2];
+        cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
+        cok[threadIdx.x] = sim_params_ok(l, m, k);
+    }
+    const bool live = t0 + threadIdx.x < len;
+    const int64_t e = b0 + t0 + threadIdx.x;
+    double st[D], ref[D], u[M];
+#pragma unroll
+    for (int i = 0; i < D; ++i) st[i] = ref[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) u[i] = 0.0;
+    if (live) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) st[i] = sin_[(int64_t)i * n_env + e];
+#pragma unroll
+        for (int i = 0; i < M; ++i) u[i] = act[(int64_t)i * n_env + e];
+#pragma unroll
+        for (int i = 0; i < D; ++i) ref[i] = next_ref[(int64_t)i * n_env + e];
+    }
+    double th0[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) th0[i] = st[2 + 2 * i];
+    const bool in_range = sw::track_angle_range<N>(0.0, th0) < sw::kAngleLimit;
+    double ie[3] = {0.0, 0.0, 0.0};
+    if (NP == 7) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) ie[i] = inv_2e[s * 3 + i];
+    }
+    __syncthreads();
+    bool ok = in_range;
+    double r0[D], rp[D], J0[D], J1[D], J2[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) r0[i] = rp[i] = J0[i] = J1[i] = J2[i] = 0.0;
+#pragma unroll 1
+    for (int p = 0; p < NP; ++p) {   // one copy of the step's code; the point's role is a uniform choice
+        double x = st[0], y = st[1], t[N], td[N], rew, rt[D];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            t[i] = st[2 + 2 * i];
+            td[i] = st[3 + 2 * i];
+        }
+        (void)sw::euler_step<N>(cc[p], x, y, t, td, u, rew);
+        ok = ok && cok[p];
+        rt[0] = x - ref[0];
+        rt[1] = y - ref[1];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            rt[2 + 2 * i] = t[i] - ref[2 + 2 * i];
+            rt[3 + 2 * i] = td[i] - ref[3 + 2 * i];
+        }
+        if (p == 0) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) r0[i] = rt[i];
+        } else if (p & 1) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) rp[i] = rt[i];
+        } else {
+            const double inv = p == 2 ? ie[0] : p == 4 ? ie[1] : ie[2];
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                const double j = (rp[i] - rt[i]) * inv;
+                J0[i] = p == 2 ? j : J0[i];
+                J1[i] = p == 4 ? j : J1[i];
+                J2[i] = p == 6 ? j : J2[i];
+            }
+        }
+    }
+    double acc[K];
+#pragma unroll
+    for (int v = 0; v < K; ++v) acc[v] = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        acc[0] = __builtin_fma(r0[i], r0[i], acc[0]);
+        if (NP == 7) {
+            acc[1] = __builtin_fma(J0[i], J0[i], acc[1]);
+            acc[2] = __builtin_fma(J0[i], J1[i], acc[2]);
+            acc[3] = __builtin_fma(J0[i], J2[i], acc[3]);
+            acc[5] = __builtin_fma(J1[i], J1[i], acc[5]);
+            acc[6] = __builtin_fma(J1[i], J2[i], acc[6]);
+            acc[9] = __builtin_fma(J2[i], J2[i], acc[9]);
+            acc[10] = __builtin_fma(J0[i], r0[i], acc[10]);
+            acc[11] = __builtin_fma(J1[i], r0[i], acc[11]);
+            acc[12] = __builtin_fma(J2[i], r0[i], acc[12]);
+        }
+    }
+    if (NP == 7) {   // J^T J is symmetric: the lower triangle is the upper one's bits
+        acc[4] = acc[2];
+        acc[7] = acc[3];
+        acc[8] = acc[6];
+    }
+#pragma unroll
+    for (int v = 0; v < K; ++v) {
+        double a = live ? (ok ? acc[v] : __builtin_nan("")) : 0.0;
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) a += __shfl_down(a, off, kWave);
+        if (threadIdx.x % kWave == 0) wsum[v][threadIdx.x / kWave] = a;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        double t = wsum[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
+        partial[(s * K + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
+    }
+    if (set_status && blockIdx.x == 0 && threadIdx.x == 0) {
+        bool all = true;
+        for (int p = 0; p < NP; ++p) all = all && cok[p];
+        set_status[s] = all ? SW_STATUS_OK : SW_STATUS_PARAM;
+    }
+}
+
 template <int N, bool TWIN>
 __global__ void __launch_bounds__(kStepBlock)
 accel_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restrict__ sin_,
@@ -424,6 +715,65 @@ int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double
         hipLaunchKernelGGL(residual_rows_sum_kernel, dim3((unsigned)n_cand), dim3(kWave), 0, (hipStream_t)stream, nb,
                            partial, value);
     }
+    return launch_status();
+}
+
+int sw_step_residual_sets_f64(const sw_params *base, int64_t n_set, const int64_t *set_begin, int64_t max_set_len,
+                              int64_t n_cand, const double *cand, const int32_t *cand_set, int64_t n_env,
+                              const double *state, const double *action, const double *next_ref, double *partial,
+                              double *value, int32_t *cand_status, void *stream)
+{
+    int rc = check_params(base);
+    if (rc) return rc;
+    if (!set_begin || !cand || !cand_set || !state || !action || !next_ref || !partial) return SW_ERR_NULL;
+    if (n_set < 1 || n_cand < 1 || n_cand > kPopMaxCandidates || max_set_len < 1 || n_env < 1 || max_set_len > n_env)
+        return SW_ERR_SIZE;
+    if (is_twin(base)) return SW_ERR_PARAM;
+    const sw::Consts C = make_consts(base);    // h and the direction; l_i, m_i, k come from each candidate
+    const int64_t nb = (max_set_len + kStepBlock - 1) / kStepBlock;
+    const dim3 grid((unsigned)nb, (unsigned)((n_cand + kPopGroup - 1) / kPopGroup));
+    const bool known_n = with_n<2, 8>(base->n, [&](auto N) {
+        hipLaunchKernelGGL((step_residual_sets_kernel<N.value>), grid, dim3(kStepBlock), 0, (hipStream_t)stream, C,
+                           n_set, set_begin, max_set_len, n_cand, cand, cand_set, n_env, state, action, next_ref,
+                           partial, cand_status);
+    });
+    if (!known_n) return SW_ERR_SEGMENTS;
+    if (value) {
+        rc = launch_status();
+        if (rc) return rc;
+        hipLaunchKernelGGL(residual_set_rows_sum_kernel, dim3((unsigned)n_cand), dim3(kWave), 0, (hipStream_t)stream,
+                           n_set, set_begin, max_set_len, n_env, cand_set, 1, (const int32_t *)nullptr, nb, partial,
+                           value);
+    }
+    return launch_status();
+}
+
+int sw_step_residual_normal_sets_f64(const sw_params *base, int64_t n_set, const int64_t *set_begin,
+                                     int64_t max_set_len, int32_t n_point, const double *points, const double *inv_2e,
+                                     const int32_t *active, int64_t n_env, const double *state, const double *action,
+                                     const double *next_ref, double *partial, double *out, int32_t *set_status,
+                                     void *stream)
+{
+    int rc = check_params(base);
+    if (rc) return rc;
+    if (!set_begin || !points || !state || !action || !next_ref || !partial || !out) return SW_ERR_NULL;
+    if (n_point == 7 && !inv_2e) return SW_ERR_NULL;
+    if (n_set < 1 || n_set > kSetsMax || max_set_len < 1 || n_env < 1 || max_set_len > n_env) return SW_ERR_SIZE;
+    if (is_twin(base) || (n_point != 1 && n_point != 7)) return SW_ERR_PARAM;
+    const sw::Consts C = make_consts(base);
+    const int64_t nb = (max_set_len + kStepBlock - 1) / kStepBlock;
+    const dim3 grid((unsigned)nb, (unsigned)n_set);
+    const bool known_n = with_n<2, 8>(base->n, [&](auto N, auto NORMAL) {
+        hipLaunchKernelGGL((step_residual_normal_sets_kernel<N.value, NORMAL.value ? 7 : 1>), grid, dim3(kStepBlock),
+                           0, (hipStream_t)stream, C, n_set, set_begin, max_set_len, points, inv_2e, active, n_env,
+                           state, action, next_ref, partial, set_status);
+    }, n_point == 7);
+    if (!known_n) return SW_ERR_SEGMENTS;
+    rc = launch_status();
+    if (rc) return rc;
+    const int K = n_point == 7 ? 13 : 1;
+    hipLaunchKernelGGL(residual_set_rows_sum_kernel, dim3((unsigned)(n_set * K)), dim3(kWave), 0, (hipStream_t)stream,
+                       n_set, set_begin, max_set_len, n_env, (const int32_t *)nullptr, K, active, nb, partial, out);
     return launch_status();
 }
 

@@ -97,6 +97,86 @@ def step_residual_population(p_base: SwParams, cand, state, action, next_ref, pa
     return value, partial, status
 
 
+def _want_typed(t, name, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.SwimmerHipError(f"{name}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, "
+                                   f"got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref):
+    T = state.shape[1]
+    _want(state, "state", (p_base.d, T))
+    _want(action, "action", (p_base.m, T))
+    _want(next_ref, "next_ref", (p_base.d, T))
+    if set_begin.dim() != 1 or set_begin.shape[0] < 2:
+        raise _lib.SwimmerHipError(f"set_begin: expected int64 tensor of shape (n_set + 1,), got {tuple(set_begin.shape)}")
+    n_set = set_begin.shape[0] - 1
+    _want_typed(set_begin, "set_begin", torch.int64, (n_set + 1,))
+    return T, n_set, int(load().sw_step_residual_blocks(int(max_set_len)))
+
+
+def step_residual_sets(p_base: SwParams, set_begin, max_set_len: int, cand, cand_set, state, action, next_ref,
+                       partial=None, value=None, status=None):
+    """step_residual_population for candidates that score on different transition sets, in one launch
+    (sw_step_residual_sets_f64): set s is columns [set_begin[s], set_begin[s + 1]) of the concatenated transitions
+    (set_begin int64 [n_set + 1] on the device, max_set_len the longest set), candidate j = cand[j] (l_i, m_i, k)
+    scores on set cand_set[j] (int32 [n_cand], ascending).  Returns (value [n_cand], partial [n_cand,
+    step_residual_blocks(max_set_len)], status [n_cand]): the first step_residual_blocks(len of j's set) entries of
+    partial[j] have the bits step_residual gives for candidate j on its set's slice (the rest is not written),
+    value[j] is their fixed-order sum."""
+    require_gpu()
+    T, n_set, nb = _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref)
+    if cand.dim() != 2 or cand.shape[0] < 1:
+        raise _lib.SwimmerHipError(f"cand: expected float64 tensor of shape (n_cand, 3), got {tuple(cand.shape)}")
+    n_cand = cand.shape[0]
+    _want_typed(cand, "cand", torch.float64, (n_cand, 3))
+    _want_typed(cand_set, "cand_set", torch.int32, (n_cand,))
+    partial = _f64((n_cand, nb), state.device) if partial is None else _want(partial, "partial", (n_cand, nb))
+    value = _f64((n_cand,), state.device) if value is None else _want(value, "value", (n_cand,))
+    if status is None:
+        status = torch.zeros((n_cand,), dtype=torch.int32, device=state.device)
+    else:
+        _want_typed(status, "status", torch.int32, (n_cand,))
+    check(load().sw_step_residual_sets_f64(ctypes.byref(p_base), n_set, ptr(set_begin), int(max_set_len), n_cand,
+                                           ptr(cand), ptr(cand_set), T, ptr(state), ptr(action), ptr(next_ref),
+                                           ptr(partial), ptr(value), ptr(status), stream_ptr()),
+          "sw_step_residual_sets_f64")
+    return value, partial, status
+
+
+def step_residual_normal_sets(p_base: SwParams, set_begin, max_set_len: int, points, state, action, next_ref,
+                              inv_2e=None, active=None, partial=None, out=None, status=None):
+    """The least-squares refinement's sums per transition set, fused (sw_step_residual_normal_sets_f64): points
+    [n_set, n_point, 3] = (l_i, m_i, k).  n_point = 1: out [n_set, 1] = r.r with r = step - next_ref over the set;
+    n_point = 7 (centre, +e0, -e0, +e1, -e1, +e2, -e2, with inv_2e [n_set, 3]): out [n_set, 13] = r.r | J^T J | J^T r,
+    J by central differences.  active (int32 [n_set]): sets with 0 are neither read nor written.  Returns (out,
+    status [n_set])."""
+    require_gpu()
+    T, n_set, nb = _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref)
+    if points.dim() != 3:
+        raise _lib.SwimmerHipError(f"points: expected float64 tensor of shape (n_set, n_point, 3), got "
+                                   f"{tuple(points.shape)}")
+    n_point = points.shape[1]
+    _want_typed(points, "points", torch.float64, (n_set, n_point, 3))
+    K = 13 if n_point == 7 else 1
+    if inv_2e is not None:
+        _want_typed(inv_2e, "inv_2e", torch.float64, (n_set, 3))
+    if active is not None:
+        _want_typed(active, "active", torch.int32, (n_set,))
+    partial = _f64((n_set, K, nb), state.device) if partial is None else _want(partial, "partial", (n_set, K, nb))
+    out = _f64((n_set, K), state.device) if out is None else _want(out, "out", (n_set, K))
+    if status is None:
+        status = torch.zeros((n_set,), dtype=torch.int32, device=state.device)
+    else:
+        _want_typed(status, "status", torch.int32, (n_set,))
+    check(load().sw_step_residual_normal_sets_f64(ctypes.byref(p_base), n_set, ptr(set_begin), int(max_set_len),
+                                                  n_point, ptr(points), ptr(inv_2e), ptr(active), T, ptr(state),
+                                                  ptr(action), ptr(next_ref), ptr(partial), ptr(out), ptr(status),
+                                                  stream_ptr()), "sw_step_residual_normal_sets_f64")
+    return out, status
+
+
 class StepPlan(object):
     """A pre-bound sw_step_f64 launch: all argument conversion is done once, `launch()` is a
     single foreign call (the per-launch Python overhead of `step()` is larger than the 8192-env
