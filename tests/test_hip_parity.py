@@ -290,6 +290,16 @@ def test_rollout_batch_vs_oracle_and_moments(sw, kernel):
         ms = mom.sum(0).cpu().numpy()
         assert np.allclose(ms[:d], x.sum(0), rtol=1e-9, atol=1e-9)
         assert np.allclose(ms[d:], (x * x).sum(0), rtol=1e-9, atol=1e-9)
+        # ... and row by row: row b holds rollouts 16 b .. 16 b + 15 and no other (a row written to the wrong block, or
+        # a rollout counted in its neighbour's row, leaves the sum over all rows as it was).  Every term may be off by
+        # TRAJ_TOL of its size, so a row by that much of its sum of absolute terms.
+        rows = mom.cpu().numpy()
+        xr = ref_traj - c
+        assert rows.shape[0] == -(-R // 16)
+        for b in range(rows.shape[0]):
+            xb = xr[16 * b:16 * (b + 1)].reshape(-1, d)
+            assert (np.abs(rows[b, :d] - xb.sum(0)) <= 1e-9 * np.maximum(1.0, np.abs(xb).sum(0))).all(), (n, R, b)
+            assert (np.abs(rows[b, d:] - (xb * xb).sum(0)) <= 1e-9 * np.maximum(1.0, (xb * xb).sum(0))).all(), (n, R, b)
         # full moments kernel over the recorded trajectories
         acc_dev = sw.kernels.traj_moments(p, traj)
         acc = acc_dev[:1 + d + d * d].cpu().numpy()
