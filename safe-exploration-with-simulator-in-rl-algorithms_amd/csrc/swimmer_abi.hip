@@ -1,7 +1,7 @@
 // swimmer_abi.hip -- the rollout side of the C ABI of include/swimmer_hip.h: which kernel form a launch takes
-// (plan_rollouts) and the one dispatcher over the forms' launch functions, the rollout / gate / safe-rollout entry
-// points, the issue probe, and the native ARS iteration pipeline.  (The step, update and covariance entry points are in
-// the files of their kernels.)
+// (plan_rollouts, plan_multi) and the one dispatch over the forms' tables of launch functions (launchers), the rollout /
+// gate / safe-rollout entry points, the issue probe, and the native ARS iteration pipeline.  (The step, update and
+// covariance entry points are in the files of their kernels.)
 #include <chrono>
 #include <new>
 #include <vector>
@@ -47,16 +47,29 @@ __global__ void __launch_bounds__(256) issue_probe_kernel(int32_t trips, int32_t
     out[threadIdx.x % kWave] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + (double)(b0 ^ b1 ^ b2 ^ b3 ^ b4 ^ b5 ^ b6 ^ b7);
 }
 
-constexpr int64_t kOctMaxRollouts = 8192;
+// The one dispatch over the forms: every launch goes through the table of its plan's form.
+const FormLaunchers &launchers(Form form)
+{
+    switch (form) {
+    case Form::Oct3: return kOct3Launchers;
+    case Form::Quad3: return kQuad3Launchers;
+    case Form::Row: return kRowLaunchers;
+    case Form::Lane: break;
+    }
+    return kLaneLaunchers;
+}
 
 // Kernel choice for rollouts: a segment-per-lane kernel while it still finds idle SIMDs, the
 // lane-per-rollout kernel beyond; sw_params.flags can force either.
 //  * n = 3 with lane roles (two mirror quads per rollout, swimmer_oct3.h): 8 rollouts per wave, so it
 //    keeps one wave per SIMD up to 8192 rollouts; beyond that the quad kernel (16 per wave) takes over.
-//    SWIMMER_N3_KERNEL=quad|oct overrides the default (measurement knob).  allow_quad = false: the
-//    caller has no quad kernel (safe rollouts).
+//    SWIMMER_N3_KERNEL=quad|oct overrides the default (measurement knob).
 //  * n = 4..8: the row kernel.
-RolloutPlan plan_rollouts(const sw_params *p, int64_t n_roll, int32_t H, bool with_traj, bool allow_quad = true)
+// op: the member of FormLaunchers that will launch the plan.  THE FALLBACK RULE: a form whose table has no entry for
+// the operation hands the launch to the lane form -- safe rollouts where the quad form would run (n = 3 beyond 8192
+// rollouts), the safe-ARS rollouts of a batch of agents wherever the mirror-quad form would not.
+template <class Member>
+RolloutPlan plan_rollouts(const sw_params *p, Member FormLaunchers::*op, int64_t n_roll, int32_t H, bool with_traj)
 {
     static const char *env = getenv("SWIMMER_N3_KERNEL");
     const bool want_oct = env ? (env[0] == 'o') : SW_N3_DEFAULT_OCT;
@@ -68,10 +81,7 @@ RolloutPlan plan_rollouts(const sw_params *p, int64_t n_roll, int32_t H, bool wi
             // the quad and mirror-quad kernels address the trajectory buffer with 32-bit byte offsets
             const bool fits = !(with_traj && (int64_t)H * 8 * n_roll * 8 >= ((int64_t)1 << 32)) &&
                               n_roll < ((int64_t)1 << 25) && (uncapped || n_roll <= kQuadMaxRollouts);
-            if (fits && want_oct && n_roll <= kOctMaxRollouts)
-                form = Form::Oct3;
-            else if (fits && allow_quad)
-                form = Form::Quad3;
+            if (fits) form = want_oct && n_roll <= kOctMaxRollouts ? Form::Oct3 : Form::Quad3;
         } else if (p->n >= 4) {
             const bool fits =
                 !(with_traj && (int64_t)H * (2 * p->n + 2) * n_roll * 8 >= ((int64_t)1 << 32) - 256) &&
@@ -79,7 +89,8 @@ RolloutPlan plan_rollouts(const sw_params *p, int64_t n_roll, int32_t H, bool wi
             if (fits) form = Form::Row;
         }
     }
-    const int per_block = form == Form::Lane ? kRollBlock : kMomGroup;   // rollouts per workgroup
+    if (!(launchers(form).*op)) form = Form::Lane;
+    const int per_block = form_slots(form);   // rollouts per workgroup
     return RolloutPlan{form, form_block(form), (unsigned)((n_roll + per_block - 1) / per_block), form != Form::Lane};
 }
 
@@ -92,13 +103,32 @@ int launch_rollouts(const sw_params *p, const RolloutPlan &plan, bool ars, int64
 {
     if (!a.policies || !a.returns) return SW_ERR_NULL;
     if ((a.mean == nullptr) != (a.inv_std == nullptr)) return SW_ERR_NULL;
-    switch (plan.form) {
-    case Form::Oct3: return launch_oct3(p, plan, ars, n_roll, H, a, stream, side);
-    case Form::Quad3: return launch_quad3(p, plan, ars, n_roll, H, a, stream, side);
-    case Form::Row: return launch_row(p, plan, ars, n_roll, H, a, stream, side);
-    case Form::Lane: break;
-    }
-    return launch_lane(p, plan, ars, n_roll, H, a, stream, side);
+    return launchers(plan.form).rollouts(p, plan, ars, n_roll, H, a, stream, side);
+}
+
+// The plan of a launch for n_agent agents (same model, same n_dir, same H), and THE SIZE RULE of such launches.  Every
+// agent gets whole workgroups: form_slots(form) * ceil(2 n_dir / form_slots(form)) rollout slots, so a workgroup's base
+// pointers are uniform and a moment row never holds two agents.  The form is chosen from the slot count of the WHOLE
+// launch at the 16-slot granule: that count is what decides whether a segment-per-lane kernel still finds an idle SIMD
+// per wave.  with_capture: the safe-ARS cost trace (32-bit byte offsets in the mirror-quad form, as for a trajectory).
+struct MultiPlan {
+    RolloutPlan plan;
+    bool in_range;   // n_agent 1..65535 (grid.y), n_dir 1..2^23 (rollouts indexed like a single launch's), H >= 0
+    bool fits;       // ... and fewer than 2^32 threads in the launch: the plan can be launched
+};
+template <class Member>
+MultiPlan plan_multi(const sw_params *p, Member FormLaunchers::*op, int64_t n_agent, int64_t n_dir, int32_t H,
+                     bool with_capture = false)
+{
+    MultiPlan m{};
+    m.in_range = n_agent >= 1 && n_agent <= 65535 && n_dir >= 1 && n_dir <= ((int64_t)1 << 23) && H >= 0;
+    if (!m.in_range) return m;
+    const int64_t n_roll = 2 * n_dir;
+    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
+    m.plan = plan_rollouts(p, op, slots, H, with_capture);
+    const dim3 grid = multi_grid(m.plan, n_agent, n_roll);
+    m.fits = (int64_t)grid.x * grid.y * m.plan.block < ((int64_t)1 << 32);
+    return m;
 }
 
 }  // namespace
@@ -161,8 +191,8 @@ int sw_rollout_f64(const sw_params *p, int64_t n_roll, int32_t H, const double *
     if (n_roll == 0) return SW_OK;
     const RolloutArgs a{policies, /*deltas=*/nullptr, /*dir_begin=*/0, /*nu=*/0.0, mean, inv_std, state0,
                         returns,  traj, final_state, moments, status};
-    return launch_rollouts(p, plan_rollouts(p, n_roll, H, traj != nullptr), false, n_roll, H, a,
-                           (hipStream_t)stream);
+    return launch_rollouts(p, plan_rollouts(p, &FormLaunchers::rollouts, n_roll, H, traj != nullptr), false, n_roll,
+                           H, a, (hipStream_t)stream);
 }
 
 int sw_safe_rollouts_f64(const sw_params *real, const sw_params *sim, int64_t n_roll, int32_t H,
@@ -181,12 +211,10 @@ int sw_safe_rollouts_f64(const sw_params *real, const sw_params *sim, int64_t n_
     if (!(sim_thresh == sim_thresh) || !(real_thresh == real_thresh)) return SW_ERR_PARAM;
     if (n_roll == 0) return SW_OK;
     if (!policies || !returns) return SW_ERR_NULL;
-    const RolloutPlan plan = plan_rollouts(real, n_roll, H, traj != nullptr, /*allow_quad=*/false);
-    SafeLauncher *launch = launch_safe_lane;   // (there is no safe quad kernel: allow_quad above)
-    if (plan.form == Form::Oct3) launch = launch_safe_oct3;
-    if (plan.form == Form::Row) launch = launch_safe_row;
-    return launch(real, sim, plan, n_roll, H, policies, cost_kind, cost_index, sim_thresh, real_thresh, returns, traj,
-                  first_refused, violations, status, (hipStream_t)stream);
+    const RolloutPlan plan = plan_rollouts(real, &FormLaunchers::safe, n_roll, H, traj != nullptr);
+    return launchers(plan.form).safe(real, sim, plan, n_roll, H, policies, cost_kind, cost_index, sim_thresh,
+                                     real_thresh, returns, traj, first_refused, violations, status,
+                                     (hipStream_t)stream);
 }
 
 int sw_ars_rollouts_f64(const sw_params *p, int64_t dir_begin, int64_t n_dir, int32_t H,
@@ -201,8 +229,8 @@ int sw_ars_rollouts_f64(const sw_params *p, int64_t dir_begin, int64_t n_dir, in
     if (!deltas) return SW_ERR_NULL;
     const RolloutArgs a{policy,  deltas, dir_begin, nu, mean, inv_std, /*state0=*/nullptr,
                         returns, traj, /*final_state=*/nullptr, moments, status};
-    return launch_rollouts(p, plan_rollouts(p, 2 * n_dir, H, traj != nullptr), true, 2 * n_dir, H, a,
-                           (hipStream_t)stream);
+    return launch_rollouts(p, plan_rollouts(p, &FormLaunchers::rollouts, 2 * n_dir, H, traj != nullptr), true,
+                           2 * n_dir, H, a, (hipStream_t)stream);
 }
 
 // The ARS simulator gate (ars_agent.py:144-157): the 2 n_dir simulator rollouts of sw_ars_rollouts_f64 in
@@ -218,65 +246,31 @@ int sw_ars_gate_f64(const sw_params *sim, int64_t dir_begin, int64_t n_dir, int3
     if (!policy || !deltas || !admit) return SW_ERR_NULL;
     if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
     const int64_t n_roll = 2 * n_dir;
-    const hipStream_t st = (hipStream_t)stream;
-    const RolloutPlan plan = plan_rollouts(sim, n_roll, H, false);
+    const RolloutPlan plan = plan_rollouts(sim, &FormLaunchers::gate, n_roll, H, false);
     const RolloutArgs a{policy,  deltas, dir_begin, nu, mean, inv_std, /*state0=*/nullptr,
                         returns, /*traj=*/nullptr, /*final_state=*/nullptr, /*moments=*/nullptr, status};
-    switch (plan.form) {
-    case Form::Oct3: return launch_gate_oct3(sim, plan, n_roll, H, a, sim_thresh, admit, st);
-    case Form::Quad3: return launch_gate_quad3(sim, plan, n_roll, H, a, sim_thresh, admit, st);
-    case Form::Row: return launch_gate_row(sim, plan, n_roll, H, a, sim_thresh, admit, st);
-    case Form::Lane: break;
-    }
-    return launch_gate_lane(sim, plan, n_roll, H, a, sim_thresh, admit, st);
+    return launchers(plan.form).gate(sim, plan, n_roll, H, a, sim_thresh, admit, (hipStream_t)stream);
 }
 
-// The ARS rollouts of n_agent agents (same model, same n_dir, same H) in one launch.  Every agent gets whole
-// workgroups: form_slots(form) * ceil(2 n_dir / form_slots(form)) rollout slots, so a workgroup's base pointers are
-// uniform and a moment row never holds two agents.  The form is chosen from the slot count of the WHOLE launch at the
-// 16-slot granule: that count is what decides whether a segment-per-lane kernel still finds an idle SIMD per wave.
+// The ARS rollouts of n_agent agents in one launch (plan_multi); the pointers come before the agent and direction limits.
 int sw_ars_rollouts_multi_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, int32_t H, const double *policy,
                               const double *deltas, double nu, const double *mean, const double *inv_std,
                               double *returns, double *moments, int32_t *status, void *stream)
 {
     int rc = check_params(p);
     if (rc) return rc;
-    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;
+    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;   // an empty or negative batch: before the pointers
     if (!policy || !deltas || !returns) return SW_ERR_NULL;
     if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
-    // grid.y carries the agent; an agent's rollouts are indexed like a single launch's
-    if (n_agent > 65535 || n_dir > ((int64_t)1 << 23)) return SW_ERR_SIZE;
-    const int64_t n_roll = 2 * n_dir;
-    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
-    const RolloutPlan plan = plan_rollouts(p, slots, H, false);
-    const dim3 grid = multi_grid(plan, n_agent, n_roll);
-    if ((int64_t)grid.x * grid.y * plan.block >= ((int64_t)1 << 32)) return SW_ERR_SIZE;   // threads of one launch
+    const MultiPlan m = plan_multi(p, &FormLaunchers::multi, n_agent, n_dir, H);
+    if (!m.fits) return SW_ERR_SIZE;
     const MultiArgs a{policy, deltas, mean, inv_std, returns, moments, status};
-    const hipStream_t st = (hipStream_t)stream;
-    switch (plan.form) {
-    case Form::Oct3: return launch_multi_oct3(p, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Quad3: return launch_multi_quad3(p, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Row: return launch_multi_row(p, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Lane: break;
-    }
-    return launch_multi_lane(p, plan, n_agent, n_roll, H, a, nu, st);
+    return launchers(m.plan.form).multi(p, m.plan, n_agent, 2 * n_dir, H, a, nu, (hipStream_t)stream);
 }
 
 // The safe half of a batch of agents.  Both entry points choose the form and the grid as sw_ars_rollouts_multi_f64
 // does (from the slot count of the whole launch, at the maximum n_dir for the counted rollouts: a form must not
 // depend on values the host has not seen).
-static int plan_safe_multi(const sw_params *p, int64_t n_agent, int64_t n_dir, int32_t H, RolloutPlan *plan)
-{
-    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;
-    if (n_agent > 65535 || n_dir > ((int64_t)1 << 23)) return SW_ERR_SIZE;
-    const int64_t n_roll = 2 * n_dir;
-    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
-    *plan = plan_rollouts(p, slots, H, false);
-    const dim3 grid = multi_grid(*plan, n_agent, n_roll);
-    if ((int64_t)grid.x * grid.y * plan->block >= ((int64_t)1 << 32)) return SW_ERR_SIZE;   // threads of one launch
-    return SW_OK;
-}
-
 int sw_ars_gate_multi_f64(const sw_params *base, int64_t n_agent, int64_t n_dir, int32_t H, const double *policy,
                           const double *deltas, double nu, const double *mean, const double *inv_std,
                           const double *sim, const double *sim_thresh, int32_t *admit, double *returns,
@@ -284,22 +278,13 @@ int sw_ars_gate_multi_f64(const sw_params *base, int64_t n_agent, int64_t n_dir,
 {
     int rc = check_params(base);
     if (rc) return rc;
-    RolloutPlan plan;
-    rc = plan_safe_multi(base, n_agent, n_dir, H, &plan);
-    if (rc) return rc;
+    const MultiPlan m = plan_multi(base, &FormLaunchers::gate_multi, n_agent, n_dir, H);
+    if (!m.fits) return SW_ERR_SIZE;
     if (!policy || !deltas || !sim || !sim_thresh || !admit || !returns) return SW_ERR_NULL;
     if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
     const SafeMultiArgs a{policy, deltas, mean, inv_std, returns, /*moments=*/nullptr, status, sim, sim_thresh, admit,
                           /*count=*/nullptr};
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t n_roll = 2 * n_dir;
-    switch (plan.form) {
-    case Form::Oct3: return launch_gate_multi_oct3(base, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Quad3: return launch_gate_multi_quad3(base, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Row: return launch_gate_multi_row(base, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Lane: break;
-    }
-    return launch_gate_multi_lane(base, plan, n_agent, n_roll, H, a, nu, st);
+    return launchers(m.plan.form).gate_multi(base, m.plan, n_agent, 2 * n_dir, H, a, nu, (hipStream_t)stream);
 }
 
 int sw_ars_rollouts_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const int32_t *count,
@@ -309,28 +294,18 @@ int sw_ars_rollouts_multi_counted_f64(const sw_params *p, int64_t n_agent, int64
 {
     int rc = check_params(p);
     if (rc) return rc;
-    RolloutPlan plan;
-    rc = plan_safe_multi(p, n_agent, n_dir, H, &plan);
-    if (rc) return rc;
+    const MultiPlan m = plan_multi(p, &FormLaunchers::counted, n_agent, n_dir, H);
+    if (!m.fits) return SW_ERR_SIZE;
     if (!count || !policy || !deltas || !returns) return SW_ERR_NULL;
     if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
     const SafeMultiArgs a{policy, deltas, mean, inv_std, returns, moments, status, /*sim=*/nullptr,
                           /*sim_thresh=*/nullptr, /*admit=*/nullptr, count};
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t n_roll = 2 * n_dir;
-    switch (plan.form) {
-    case Form::Oct3: return launch_counted_oct3(p, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Quad3: return launch_counted_quad3(p, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Row: return launch_counted_row(p, plan, n_agent, n_roll, H, a, nu, st);
-    case Form::Lane: break;
-    }
-    return launch_counted_lane(p, plan, n_agent, n_roll, H, a, nu, st);
+    return launchers(m.plan.form).counted(p, m.plan, n_agent, 2 * n_dir, H, a, nu, (hipStream_t)stream);
 }
 
 // The exploration rollouts of a batch of Basic_ARS / Safe_ARS agents (safe_ars/experiment.py): the form and the grid
 // as sw_ars_rollouts_multi_f64 chooses them, with two forms to choose from -- mirror-quad where the plan says so
-// (n = 3), one rollout per lane everywhere else.  A cost trace counts as capture: the mirror-quad form addresses it
-// with 32-bit byte offsets, and the plan's test for a trajectory of 8 doubles per step covers its one.
+// (n = 3), one rollout per lane everywhere else (plan_rollouts' fallback rule).  A cost trace counts as capture.
 int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64_t n_dir, int32_t H,
                                    const double *policy, const double *deltas, double nu, const int32_t *gated,
                                    const double *sim, const double *sim_thresh, const double *real_thresh,
@@ -340,21 +315,16 @@ int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64
 {
     int rc = check_params(real);
     if (rc) return rc;
-    if (n_agent < 1 || n_dir < 1 || H < 0) return SW_ERR_SIZE;
-    if (n_agent > 65535 || n_dir > ((int64_t)1 << 23)) return SW_ERR_SIZE;
+    const MultiPlan m = plan_multi(real, &FormLaunchers::safe_ars_multi, n_agent, n_dir, H, cost_trace != nullptr);
+    if (!m.in_range) return SW_ERR_SIZE;
     if (cost_kind != SW_COST_ABS_OBS && cost_kind != SW_COST_MAX_ABS_THETADOT) return SW_ERR_SIZE;
     if (cost_kind == SW_COST_ABS_OBS && (cost_index < 0 || cost_index >= 2 * real->n + 2)) return SW_ERR_SIZE;
     if (!policy || !deltas || !gated || !sim || !sim_thresh || !real_thresh || !returns) return SW_ERR_NULL;
-    const int64_t n_roll = 2 * n_dir;
-    const int64_t slots = n_agent * (((n_roll + kMomGroup - 1) / kMomGroup) * kMomGroup);
-    RolloutPlan plan = plan_rollouts(real, slots, H, cost_trace != nullptr, /*allow_quad=*/false);
-    if (plan.form != Form::Oct3) plan = RolloutPlan{Form::Lane, form_block(Form::Lane), 0u, false};   // (no row form)
-    const dim3 grid = multi_grid(plan, n_agent, n_roll);
-    if ((int64_t)grid.x * grid.y * plan.block >= ((int64_t)1 << 32)) return SW_ERR_SIZE;   // threads of one launch
+    if (!m.fits) return SW_ERR_SIZE;
     const SafeArsMultiArgs a{policy,  deltas,     gated,    sim,           sim_thresh, real_thresh,
                              returns, cost_trace, cost_max, first_refused, violations, status};
-    SafeArsMultiLauncher *launch = plan.form == Form::Oct3 ? launch_safe_ars_multi_oct3 : launch_safe_ars_multi_lane;
-    return launch(real, plan, n_agent, n_roll, H, a, nu, cost_kind, cost_index, (hipStream_t)stream);
+    return launchers(m.plan.form).safe_ars_multi(real, m.plan, n_agent, 2 * n_dir, H, a, nu, cost_kind, cost_index,
+                                                 (hipStream_t)stream);
 }
 
 // ---- ARS iteration pipeline ---------------------------------------------------------
@@ -597,7 +567,7 @@ int sw_ars_iteration_rollouts_f64(sw_ars_pipeline *pl, int slot, const sw_params
             return SW_ERR_LAUNCH;
     }
     // ONE plan for the ride-along decision below and for the launch itself
-    const RolloutPlan plan = plan_rollouts(p, 2 * n_dir, H, traj != nullptr);
+    const RolloutPlan plan = plan_rollouts(p, &FormLaunchers::rollouts, 2 * n_dir, H, traj != nullptr);
     const int cov_block = owed_cov_block(plan.form);
     SideWork sj{pl->flag_dev, k, nullptr, nullptr, 0, 0};
     // the owed pass rides along when this launch's kernel can carry it in the tiling it is owed in

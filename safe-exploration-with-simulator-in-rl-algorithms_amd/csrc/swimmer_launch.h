@@ -1,6 +1,6 @@
 // swimmer_launch.h -- what the kernel families of libswimmer_hip.so share (internal; the C ABI is
 // include/swimmer_hip.h): constants, tuning knobs, argument checks, the run-time-to-template dispatch, the rollout
-// plan, and the declarations of the launch functions that cross the files.
+// plan, and the four tables of launch functions -- one per kernel form -- that cross the files.
 //
 // All arithmetic is fp64 on the vector ALUs; there is no MFMA (the largest contraction on this
 // path is 8x8) and no LDS in the hot loops (neighbour data moves by DPP).  One source file per kernel family, each
@@ -89,8 +89,9 @@
 // with_n<LO, HI>(), next to the kernels they name.
 //
 // Kernels and the types they take stay in unnamed namespaces (their mangled names are what the ISA tools, the
-// placement test and the profiles key on), so nothing of such a type can cross a file: what does cross is in
-// namespace sw_launch below, with hidden visibility -- the library's dynamic symbols are the C ABI only.
+// placement test and the profiles key on), and so do the functions that launch them: what crosses the files is in
+// namespace sw_launch below, with hidden visibility -- the library's dynamic symbols are the C ABI only -- and of the
+// launch functions only ONE table of pointers per form (FormLaunchers), reached through launchers(plan.form).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -230,6 +231,7 @@ constexpr int kStepBlock = 256;
 constexpr int kRollBlock = 64;   // one wave per workgroup: every wave gets a SIMD to itself
 constexpr int kOctBlock = 128;   // mirror-quad kernel: 8 rollouts per wave, 16 (= one V2 moment row) per workgroup
 constexpr int kMomGroup = 16;    // rollouts per V2 moment row (same partition in every kernel)
+constexpr int64_t kOctMaxRollouts = 8192;    // mirror-quad kernel (n = 3): one wave per SIMD up to here
 constexpr int64_t kQuadMaxRollouts = 16384;  // above this every SIMD already has a wave
 constexpr int64_t kRowMaxRollouts = 8192;    // row kernel (n >= 4): 4 rollouts per wave
 constexpr int kRowBlock = 256;               // 16 rollouts = one V2 moment row per workgroup
@@ -450,8 +452,8 @@ __device__ __forceinline__ void load_policy_row(const double *__restrict__ pl,
 }  // namespace
 
 // ------------------------------------------------------------------------------------
-// What crosses the files: the plan of a rollout launch, and one launch function per kernel form.  (The attribute
-// holds for one block of the namespace: the files that define these functions repeat it.)
+// What crosses the files: the plan of a rollout launch, and one table of launch functions per kernel form.  (The
+// attribute holds for one block of the namespace: the files that define the tables repeat it.)
 namespace sw_launch __attribute__((visibility("hidden"))) {
 
 // The four forms of a rollout launch (above), chosen in one place: plan_rollouts(), swimmer_abi.hip.
@@ -513,18 +515,16 @@ CovTiling cov_tiling(int64_t n_roll, int32_t H, int block, int D, bool riding); 
 int launch_traj_moments(const sw_params *p, int64_t n_roll, int32_t H, const double *traj, double *acc, int block,
                         bool riding, void *stream);
 
-// One launch function per form, in the file of the form's kernels; they return launch_status(), or
-// SW_ERR_SEGMENTS for an n the form has no kernel for.  The entry points have validated the parameters and the
-// sizes, and cleared stale errors, already.
+// The types of a form's launch functions, one per operation.  The functions are private to the file of the form's
+// kernels; they return launch_status(), or SW_ERR_SEGMENTS for an n the form has no kernel for.  The entry points have
+// validated the parameters and the sizes, and cleared stale errors, already.
 // Rollouts (launch_rollouts, swimmer_abi.hip); side: pipeline only, and not for the lane form
 // (RolloutPlan::carries_side).
 using RolloutLauncher = int(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H,
                             const RolloutArgs &a, hipStream_t stream, const SideWork *side);
-RolloutLauncher launch_oct3, launch_quad3, launch_row, launch_lane;
 // The ARS simulator gate (sw_ars_gate_f64): a = the ARS rollouts' arguments without trajectories / moments.
 using GateLauncher = int(const sw_params *sim, const RolloutPlan &plan, int64_t n_roll, int32_t H,
                          const RolloutArgs &a, double gate_thr, int32_t *admit, hipStream_t stream);
-GateLauncher launch_gate_oct3, launch_gate_quad3, launch_gate_row, launch_gate_lane;
 // The ARS rollouts of n_agent agents in one launch (sw_ars_rollouts_multi_f64).  Every array is the single-agent
 // array of sw_ars_rollouts_f64 once per agent, agent-major and dense: policy [n_agent][m][d], deltas
 // [n_agent][n_dir][m][d], mean / inv_std [n_agent][d] (both null: V1), returns / status [n_agent][2 n_dir],
@@ -540,11 +540,17 @@ constexpr int form_slots(Form f) { return f == Form::Lane ? kRollBlock : kMomGro
 // n_roll = 2 n_dir rollouts per agent; grid = (workgroups per agent, n_agent), blocks of plan.block threads.
 using MultiLauncher = int(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                           const MultiArgs &a, double nu, hipStream_t stream);
-MultiLauncher launch_multi_oct3, launch_multi_quad3, launch_multi_row, launch_multi_lane;
 inline dim3 multi_grid(const RolloutPlan &plan, int64_t n_agent, int64_t n_roll)
 {
     const int per = form_slots(plan.form);
     return dim3((unsigned)((n_roll + per - 1) / per), (unsigned)n_agent);
+}
+// one launch of a multi-agent kernel on that grid
+template <class Kernel, class... Args>
+void launch_agent_grid(Kernel *kernel, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, hipStream_t stream,
+                       const Args &...args)
+{
+    hipLaunchKernelGGL(kernel, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0, stream, args...);
 }
 // The safe half of a batch of agents (sw_ars_gate_multi_f64, sw_ars_rollouts_multi_counted_f64): MultiArgs plus, for
 // the gate, every agent's simulator (sim [n_agent][3] = l_i, m_i, k), simulator threshold and admit flags
@@ -560,18 +566,14 @@ struct SafeMultiArgs {
 };
 using SafeMultiLauncher = int(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                               const SafeMultiArgs &a, double nu, hipStream_t stream);
-SafeMultiLauncher launch_gate_multi_oct3, launch_gate_multi_quad3, launch_gate_multi_row, launch_gate_multi_lane;
-SafeMultiLauncher launch_counted_oct3, launch_counted_quad3, launch_counted_row, launch_counted_lane;
-// Safe exploration (sw_safe_rollouts_f64); there is no safe quad kernel.
+// Safe exploration (sw_safe_rollouts_f64).
 using SafeLauncher = int(const sw_params *real, const sw_params *sim, const RolloutPlan &plan, int64_t n_roll,
                          int32_t H, const double *policies, int32_t cost_kind, int32_t cost_index, double sim_thresh,
                          double real_thresh, double *returns, double *traj, int32_t *first_refused,
                          int32_t *violations, int32_t *status, hipStream_t stream);
-SafeLauncher launch_safe_oct3, launch_safe_row, launch_safe_lane;
 // Safe exploration for the ARS rollouts of n_agent agents (sw_safe_ars_rollouts_multi_f64): agent-major arrays as in
 // MultiArgs, plus per agent gated [n_agent], sim [n_agent][3], sim_thresh / real_thresh [n_agent]; cost_trace
 // [H][n_agent][2 n_dir]; cost_max / first_refused / violations / status [n_agent][2 n_dir] (null: not wanted).
-// There is a mirror-quad form (n = 3) and a lane form (every n).
 struct SafeArsMultiArgs {
     const double *policy, *deltas;
     const int32_t *gated;
@@ -582,6 +584,17 @@ struct SafeArsMultiArgs {
 using SafeArsMultiLauncher = int(const sw_params *real, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll,
                                  int32_t H, const SafeArsMultiArgs &a, double nu, int32_t cost_kind,
                                  int32_t cost_index, hipStream_t stream);
-SafeArsMultiLauncher launch_safe_ars_multi_oct3, launch_safe_ars_multi_lane;
+// A form's launch functions by operation, defined in the file of the form's kernels; nullptr: the form has no kernel
+// for it, and plan_rollouts() hands the launch to the lane form, which has them all.  (Const members, not const tables:
+// the device pass of the compile would emit a const table too, and has no launch functions to point it at.)
+struct FormLaunchers {
+    RolloutLauncher *const rollouts;
+    GateLauncher *const gate;
+    MultiLauncher *const multi;
+    SafeMultiLauncher *const gate_multi, *const counted;
+    SafeLauncher *const safe;                     // (none in the quad form)
+    SafeArsMultiLauncher *const safe_ars_multi;   // (mirror-quad and lane only; swimmer_rollout_safe_multi.hip)
+};
+extern FormLaunchers kOct3Launchers, kQuad3Launchers, kRowLaunchers, kLaneLaunchers;
 
 }  // namespace sw_launch

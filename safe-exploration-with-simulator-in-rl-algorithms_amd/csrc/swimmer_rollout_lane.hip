@@ -114,9 +114,8 @@ safe_rollout_kernel(sw::Consts Creal, sw::Consts Csim, int64_t n_roll, int32_t H
 #undef SW_SAFE_MULTI
 }
 
-}  // namespace
-
-namespace sw_launch __attribute__((visibility("hidden"))) {
+// ---- host: the form's launch functions (private) and its table of them (sw_launch) ----
+using namespace sw_launch;
 
 int launch_lane(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H, const RolloutArgs &a,
                 hipStream_t stream, const SideWork *)
@@ -151,8 +150,8 @@ int launch_multi_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_age
     const sw::Consts C = make_consts(p);
     const sw::TwinConsts T = make_twin_consts(p);
     const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
-        hipLaunchKernelGGL((ars_multi_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
-                           dim3(plan.block), 0, stream, C, T, n_roll, H, a, nu);
+        launch_agent_grid(ars_multi_lane_kernel<N.value, TWIN.value>, plan, n_agent, n_roll, stream, C, T, n_roll, H, a,
+                          nu);
     }, is_twin(p));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -161,8 +160,8 @@ int launch_gate_multi_lane(const sw_params *p, const RolloutPlan &plan, int64_t 
                            const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
     const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
-        hipLaunchKernelGGL((ars_gate_multi_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
-                           dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu);
+        launch_agent_grid(ars_gate_multi_lane_kernel<N.value, TWIN.value>, plan, n_agent, n_roll, stream,
+                          make_consts(p), n_roll, H, a, nu);
     }, is_twin(p));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -173,8 +172,8 @@ int launch_counted_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_a
     const sw::Consts C = make_consts(p);
     const sw::TwinConsts T = make_twin_consts(p);
     const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
-        hipLaunchKernelGGL((ars_counted_lane_kernel<N.value, TWIN.value>), multi_grid(plan, n_agent, n_roll),
-                           dim3(plan.block), 0, stream, C, T, n_roll, H, a, nu);
+        launch_agent_grid(ars_counted_lane_kernel<N.value, TWIN.value>, plan, n_agent, n_roll, stream, C, T, n_roll, H,
+                          a, nu);
     }, is_twin(p));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -192,5 +191,11 @@ int launch_safe_lane(const sw_params *real, const sw_params *sim, const RolloutP
     });
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
+SafeArsMultiLauncher launch_safe_ars_multi_lane;   // swimmer_rollout_safe_multi.hip, later in the translation unit
 
+}  // namespace
+
+namespace sw_launch __attribute__((visibility("hidden"))) {
+FormLaunchers kLaneLaunchers = {launch_lane,         launch_gate_lane, launch_multi_lane, launch_gate_multi_lane,
+                                launch_counted_lane, launch_safe_lane, launch_safe_ars_multi_lane};
 }  // namespace sw_launch

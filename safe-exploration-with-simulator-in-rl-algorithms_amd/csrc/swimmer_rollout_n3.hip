@@ -226,9 +226,8 @@ safe_rollout_oct3_kernel(sw::Consts Cr, sw::Consts Cs, double tq_ratio, int64_t 
 #undef SW_SAFE_MULTI
 }
 
-}  // namespace
-
-namespace sw_launch __attribute__((visibility("hidden"))) {
+// ---- host: the form's launch functions (private) and its table of them (sw_launch) ----
+using namespace sw_launch;
 
 int launch_oct3(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H, const RolloutArgs &a,
                 hipStream_t stream, const SideWork *side)
@@ -279,8 +278,8 @@ int launch_multi_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_age
                       const MultiArgs &a, double nu, hipStream_t stream)
 {
     with_bools([&](auto MOM) {
-        hipLaunchKernelGGL(ars_multi_oct3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
-                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_multi_oct3_kernel<MOM.value>, plan, n_agent, n_roll, stream, make_consts(p), n_roll, H,
+                          a, nu, kNoSide);
     }, a.moments != nullptr);
     return launch_status();
 }
@@ -289,8 +288,8 @@ int launch_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_ag
                        const MultiArgs &a, double nu, hipStream_t stream)
 {
     with_bools([&](auto MOM) {
-        hipLaunchKernelGGL(ars_multi_quad3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
-                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_multi_quad3_kernel<MOM.value>, plan, n_agent, n_roll, stream, make_consts(p), n_roll, H,
+                          a, nu, kNoSide);
     }, a.moments != nullptr);
     return launch_status();
 }
@@ -298,16 +297,16 @@ int launch_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_ag
 int launch_gate_multi_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                            const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
-    hipLaunchKernelGGL(ars_gate_multi_oct3_kernel, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0, stream,
-                       make_consts(p), n_roll, H, a, nu, kNoSide);
+    launch_agent_grid(ars_gate_multi_oct3_kernel, plan, n_agent, n_roll, stream, make_consts(p), n_roll, H, a, nu,
+                      kNoSide);
     return launch_status();
 }
 
 int launch_gate_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                             const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
-    hipLaunchKernelGGL(ars_gate_multi_quad3_kernel, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0, stream,
-                       make_consts(p), n_roll, H, a, nu, kNoSide);
+    launch_agent_grid(ars_gate_multi_quad3_kernel, plan, n_agent, n_roll, stream, make_consts(p), n_roll, H, a, nu,
+                      kNoSide);
     return launch_status();
 }
 
@@ -315,8 +314,8 @@ int launch_counted_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_a
                         const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
     with_bools([&](auto MOM) {
-        hipLaunchKernelGGL(ars_counted_oct3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
-                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_counted_oct3_kernel<MOM.value>, plan, n_agent, n_roll, stream, make_consts(p), n_roll,
+                          H, a, nu, kNoSide);
     }, a.moments != nullptr);
     return launch_status();
 }
@@ -325,8 +324,8 @@ int launch_counted_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_
                          const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
     with_bools([&](auto MOM) {
-        hipLaunchKernelGGL(ars_counted_quad3_kernel<MOM.value>, multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
-                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_counted_quad3_kernel<MOM.value>, plan, n_agent, n_roll, stream, make_consts(p), n_roll,
+                          H, a, nu, kNoSide);
     }, a.moments != nullptr);
     return launch_status();
 }
@@ -346,5 +345,13 @@ int launch_safe_oct3(const sw_params *real, const sw_params *sim, const RolloutP
     }, traj != nullptr, violations != nullptr);
     return launch_status();
 }
+SafeArsMultiLauncher launch_safe_ars_multi_oct3;   // swimmer_rollout_safe_multi.hip, later in the translation unit
 
+}  // namespace
+
+namespace sw_launch __attribute__((visibility("hidden"))) {
+FormLaunchers kOct3Launchers = {launch_oct3,         launch_gate_oct3, launch_multi_oct3, launch_gate_multi_oct3,
+                                launch_counted_oct3, launch_safe_oct3, launch_safe_ars_multi_oct3};
+FormLaunchers kQuad3Launchers = {launch_quad3,         launch_gate_quad3, launch_multi_quad3, launch_gate_multi_quad3,
+                                 launch_counted_quad3, /*safe=*/nullptr,  /*safe_ars_multi=*/nullptr};
 }  // namespace sw_launch

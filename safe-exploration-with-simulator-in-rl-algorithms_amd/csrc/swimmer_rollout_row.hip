@@ -262,9 +262,8 @@ safe_rollout_row_kernel(sw::Consts Cr, sw::Consts Cs, int64_t n_roll, int32_t H,
     }
 }
 
-}  // namespace
-
-namespace sw_launch __attribute__((visibility("hidden"))) {
+// ---- host: the form's launch functions (private) and its table of them (sw_launch) ----
+using namespace sw_launch;
 
 int launch_row(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H, const RolloutArgs &a,
                hipStream_t stream, const SideWork *side)
@@ -289,8 +288,8 @@ int launch_multi_row(const sw_params *p, const RolloutPlan &plan, int64_t n_agen
                      const MultiArgs &a, double nu, hipStream_t stream)
 {
     const bool known_n = with_n<4, 8>(p->n, [&](auto N, auto MOM) {
-        hipLaunchKernelGGL((ars_multi_row_kernel<N.value, MOM.value>), multi_grid(plan, n_agent, n_roll),
-                           dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_multi_row_kernel<N.value, MOM.value>, plan, n_agent, n_roll, stream, make_consts(p),
+                          n_roll, H, a, nu, kNoSide);
     }, a.moments != nullptr);
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -299,8 +298,8 @@ int launch_gate_multi_row(const sw_params *p, const RolloutPlan &plan, int64_t n
                           const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
     const bool known_n = with_n<4, 8>(p->n, [&](auto N) {
-        hipLaunchKernelGGL((ars_gate_multi_row_kernel<N.value>), multi_grid(plan, n_agent, n_roll), dim3(plan.block), 0,
-                           stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_gate_multi_row_kernel<N.value>, plan, n_agent, n_roll, stream, make_consts(p), n_roll, H,
+                          a, nu, kNoSide);
     });
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -309,8 +308,8 @@ int launch_counted_row(const sw_params *p, const RolloutPlan &plan, int64_t n_ag
                        const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
     const bool known_n = with_n<4, 8>(p->n, [&](auto N, auto MOM) {
-        hipLaunchKernelGGL((ars_counted_row_kernel<N.value, MOM.value>), multi_grid(plan, n_agent, n_roll),
-                           dim3(plan.block), 0, stream, make_consts(p), n_roll, H, a, nu, kNoSide);
+        launch_agent_grid(ars_counted_row_kernel<N.value, MOM.value>, plan, n_agent, n_roll, stream, make_consts(p),
+                          n_roll, H, a, nu, kNoSide);
     }, a.moments != nullptr);
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -330,4 +329,9 @@ int launch_safe_row(const sw_params *real, const sw_params *sim, const RolloutPl
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
+}  // namespace
+
+namespace sw_launch __attribute__((visibility("hidden"))) {
+FormLaunchers kRowLaunchers = {launch_row,         launch_gate_row, launch_multi_row,          launch_gate_multi_row,
+                               launch_counted_row, launch_safe_row, /*safe_ars_multi=*/nullptr};
 }  // namespace sw_launch

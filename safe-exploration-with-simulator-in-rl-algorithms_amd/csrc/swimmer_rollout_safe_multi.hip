@@ -43,17 +43,16 @@ safe_ars_multi_lane_kernel(sw::Consts Cr, int64_t n_roll, int32_t H, sw_launch::
 #undef SW_MULTI_SLOTS
 #undef SW_MULTI_N
 
-}  // namespace
-
-namespace sw_launch __attribute__((visibility("hidden"))) {
+// ---- host: the safe_ars_multi entries of the tables in swimmer_rollout_n3.hip and swimmer_rollout_lane.hip ----
+using namespace sw_launch;
 
 int launch_safe_ars_multi_oct3(const sw_params *real, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll,
                                int32_t H, const SafeArsMultiArgs &a, double nu, int32_t cost_kind, int32_t cost_index,
                                hipStream_t stream)
 {
     with_bools([&](auto COST, auto VIOL) {
-        hipLaunchKernelGGL((safe_ars_multi_oct3_kernel<COST.value, VIOL.value>), multi_grid(plan, n_agent, n_roll),
-                           dim3(plan.block), 0, stream, make_consts(real), n_roll, H, a, nu, cost_kind, cost_index);
+        launch_agent_grid(safe_ars_multi_oct3_kernel<COST.value, VIOL.value>, plan, n_agent, n_roll, stream,
+                          make_consts(real), n_roll, H, a, nu, cost_kind, cost_index);
     }, a.cost_trace != nullptr || a.cost_max != nullptr, a.violations != nullptr);
     return launch_status();
 }
@@ -63,10 +62,10 @@ int launch_safe_ars_multi_lane(const sw_params *real, const RolloutPlan &plan, i
                                hipStream_t stream)
 {
     const bool known_n = with_n<2, 8>(real->n, [&](auto N) {
-        hipLaunchKernelGGL((safe_ars_multi_lane_kernel<N.value>), multi_grid(plan, n_agent, n_roll), dim3(plan.block),
-                           0, stream, make_consts(real), n_roll, H, a, nu, cost_kind, cost_index);
+        launch_agent_grid(safe_ars_multi_lane_kernel<N.value>, plan, n_agent, n_roll, stream, make_consts(real), n_roll,
+                          H, a, nu, cost_kind, cost_index);
     });
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
-}  // namespace sw_launch
+}  // namespace

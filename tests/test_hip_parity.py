@@ -1075,6 +1075,29 @@ def test_the_two_gate_kernel_forms_agree_at_size(sw):
     assert np.abs(out["quad"][0] - out["lane"][0]).max() <= 1e-9 * max(1.0, np.abs(out["lane"][0]).max())
 
 
+def test_safe_rollouts_beyond_the_mirror_quad_form_run_in_the_lane_form(sw):
+    """n = 3 with 8193 rollouts: one more than the mirror-quad form takes, and the quad form that plain rollouts move to
+    there has no safe kernel, so sw_safe_rollouts_f64 runs one rollout per lane -- the bits of the same call under
+    FLAG_ROLLOUT_LANE (the mirror-quad form's look-ahead differs in the last place).  H = 5: a four-step trip and a
+    remainder in the forms that are not taken; gains up to 3 so that the gate refuses some rollouts within them."""
+    rs = np.random.RandomState(8193)
+    R, H, m, d = 8193, 5, 2, 8
+    pol = torch.as_tensor(rs.uniform(0.05, 3.0, R)[:, None, None] * (2 * rs.rand(R, m, d) - 1), device="cuda:0")
+    p_sim = sw.SwParams.make(3)
+    out = {}
+    for form, flags in (("auto", 0), ("lane", sw._lib.FLAG_ROLLOUT_LANE)):
+        p_real = sw.SwParams.make(3, 0.8, 1.2, 10.2, 1e-3, flags=flags)
+        traj = torch.full((H, d, R), -7.0, dtype=torch.float64, device="cuda:0")
+        first, viol, status = (torch.full((R,), -7, dtype=torch.int32, device="cuda:0") for _ in range(3))
+        ret = sw.kernels.safe_rollouts(p_real, p_sim, H, pol, sw._lib.COST_ABS_OBS, 3, 0.05, 0.04, traj=traj,
+                                       first_refused=first, violations=viol, status=status)
+        out[form] = (ret.view(torch.int64), traj.view(torch.int64), first, viol, status)
+    for got, want in zip(out["auto"], out["lane"]):
+        assert torch.equal(got, want)
+    first = out["auto"][2]
+    assert (first >= 0).all() and (first < H).any() and (first == H).any() and (out["auto"][4] == 0).all()
+
+
 @pytest.mark.parametrize("n", [4, 6, 8])
 def test_row_form_gate_with_fast_trips(sw, n):
     """The row-form gate kernel (n = 4 ... 8) where angular velocities pass 10 rad/s -- its per-step-checked loop, in

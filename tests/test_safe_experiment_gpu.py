@@ -217,6 +217,35 @@ def test_every_lane_instantiation_runs(n):
         check_against_single_agent_kernels(mixed_case(n, 3, cost, sw._lib.FLAG_ROLLOUT_LANE), 21)
 
 
+def all_outputs(c, H):
+    """Every output of one sw_safe_ars_rollouts_multi_f64 launch of a mixed_case, as int64 / int32 tensors."""
+    A, R = 3, 2 * c["deltas"].shape[1]
+    dv = lambda x: torch.as_tensor(x, device=DEV)           # noqa: E731
+    i32 = lambda: torch.full((A, R), -7, dtype=torch.int32, device=DEV)    # noqa: E731
+    trace = torch.full((H, A, R), -7.0, dtype=torch.float64, device=DEV)
+    cmax = torch.full((A, R), -7.0, dtype=torch.float64, device=DEV)
+    first, viol, status = i32(), i32(), i32()
+    ret = sw.kernels.safe_ars_rollouts_multi(c["p"], H, dv(c["policy"]), dv(c["deltas"]), c["nu"], dv(c["gated"]),
+                                             dv(c["sim"]), dv(c["sim_thresh"]), dv(c["real_thresh"]), c["kind"],
+                                             c["index"], cost_trace=trace, cost_max=cmax, first_refused=first,
+                                             violations=viol, status=status)
+    return bits(ret), bits(trace), bits(cmax), first, viol, status
+
+
+@pytest.mark.parametrize("n,n_dir", [(4, 9), (3, 1366)], ids=["n4-no-row-form", "n3-no-quad-form"])
+def test_a_form_without_a_kernel_hands_over_to_the_lane_form(n, n_dir):
+    """Where the plan of the launch names a form that has no safe-ARS kernel -- the row form at n = 4 (18 rollouts per
+    agent: a full and a partial 16-slot group), the quad form at n = 3 with 3 x 2736 slots, more than the mirror-quad
+    form's 8192 -- the launch runs in the lane form: the bits of the same call under FLAG_ROLLOUT_LANE.  H = 5: a
+    four-step trip and a remainder in the forms that are not taken."""
+    cost = (ABS, 2 * n + 1, (0.3, 0.4), 0.004)
+    auto = all_outputs(mixed_case(n, n_dir, cost, 0), 5)
+    lane = all_outputs(mixed_case(n, n_dir, cost, sw._lib.FLAG_ROLLOUT_LANE), 5)
+    for got, want in zip(auto, lane):
+        assert torch.equal(got, want), (n, n_dir)
+    assert (auto[3] >= 0).all() and (auto[5] == 0).all()          # every rollout was run: first_refused, status written
+
+
 def test_an_agent_of_a_batch_is_the_agent_alone(g):
     """Row a of a batch of four after three training iterations, bit for bit the batch of that agent alone; both
     ways of keeping costs."""
