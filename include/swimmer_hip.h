@@ -109,6 +109,11 @@ extern "C" {
  * scalar registers, range test on vcc).  This bit keeps them on the first packed kernel.  Same outputs bit for bit;
  * for A/B measurements and for tests.  Together with SW_FLAG_CAPTURE_SPLIT it is SW_ERR_PARAM. */
 #define SW_FLAG_CAPTURE_PACKED_V1 16
+/* The same launches take one entry of a lane's 3x3 system from the neighbouring lane instead of forming it a second
+ * time (three f64 instructions fewer per step).  This bit keeps them on the lean-step kernel before that.  Same outputs
+ * bit for bit; for A/B measurements and for tests.  Together with SW_FLAG_CAPTURE_SPLIT or SW_FLAG_CAPTURE_PACKED_V1
+ * it is SW_ERR_PARAM.  (32 and 64 are not flags.) */
+#define SW_FLAG_CAPTURE_LEAN_V1 128
 
 /* sw_params.flags: which of the reference's two swimmer models the kernels integrate.
  * Default (bit clear): the Gym env (envs/gym_swimmer/swimmer/remy_swimmer_env.py, explicit

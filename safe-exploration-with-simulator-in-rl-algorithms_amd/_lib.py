@@ -25,6 +25,7 @@ FLAG_ROLLOUT_QUAD = 2   # force the segment-per-lane kernels (quad: n = 3, row: 
 FLAG_MODEL_TWIN = 4     # integrate the native RL-Glue model (SwimmerEnvironment.cpp)
 FLAG_CAPTURE_SPLIT = 8  # n = 3 with capture + V2 moments: the three-store kernel instead of the packed record form
 FLAG_CAPTURE_PACKED_V1 = 16  # the same launches: the first packed kernel instead of its lean-step successor
+FLAG_CAPTURE_LEAN_V1 = 128   # the same launches: the lean-step kernel instead of the one with the neighbour's entry
 COST_ABS_OBS = 0            # sw_safe_rollouts_f64: cost = |obs[index]|
 COST_MAX_ABS_THETADOT = 1   # cost = max_i |thetadot_i|
 
@@ -54,13 +55,14 @@ class SwimmerHipError(RuntimeError):
 
 
 def kernel_flags(name):
-    """'auto' | 'lane' | 'quad' | 'split' | 'packed_v1' -> sw_params.flags value ('split' / 'packed_v1': 'auto' with
-    FLAG_CAPTURE_SPLIT / FLAG_CAPTURE_PACKED_V1)."""
+    """'auto' | 'lane' | 'quad' | 'split' | 'packed_v1' | 'lean_v1' -> sw_params.flags value ('split' / 'packed_v1' /
+    'lean_v1': 'auto' with FLAG_CAPTURE_SPLIT / FLAG_CAPTURE_PACKED_V1 / FLAG_CAPTURE_LEAN_V1)."""
     try:
         return {"auto": 0, "lane": FLAG_ROLLOUT_LANE, "quad": FLAG_ROLLOUT_QUAD, "split": FLAG_CAPTURE_SPLIT,
-                "packed_v1": FLAG_CAPTURE_PACKED_V1}[name]
+                "packed_v1": FLAG_CAPTURE_PACKED_V1, "lean_v1": FLAG_CAPTURE_LEAN_V1}[name]
     except KeyError:
-        raise SwimmerHipError(f"rollout kernel must be 'auto', 'lane', 'quad', 'split' or 'packed_v1', not {name!r}")
+        raise SwimmerHipError("rollout kernel must be 'auto', 'lane', 'quad', 'split', 'packed_v1' or 'lean_v1', "
+                              f"not {name!r}")
 
 
 _lib = None

@@ -31,8 +31,11 @@
 //   rollout_octp3_kernel       the same with capture AND V2 moments in the packed record form: one trajectory store
 //                              and one moment pair per step (swimmer_rollout_octp3.inc); bit-identical outputs;
 //   rollout_octl3_kernel       the packed record form with a leaner step (the same body, SW_OCTP_LEAN 1): store
-//                              offsets from loop-invariant SGPRs, range test on vcc; the default of such a launch.
-//                              SW_FLAG_CAPTURE_PACKED_V1 keeps it on rollout_octp3_kernel,
+//                              offsets from loop-invariant SGPRs, range test on vcc (SW_FLAG_CAPTURE_LEAN_V1)
+//   rollout_octs3_kernel       the lean mode with the neighbour's matrix entry (SW_OCTP_NEXT_E 1): Q(i+1, i+2) comes
+//                              from lane i+1 through DPP, three f64 instructions fewer per step; the default of such
+//                              a launch.  SW_FLAG_CAPTURE_LEAN_V1 keeps it on rollout_octl3_kernel,
+//                              SW_FLAG_CAPTURE_PACKED_V1 on rollout_octp3_kernel,
 //                              SW_FLAG_CAPTURE_SPLIT on rollout_oct3_kernel<.., true, true>
 //   rollout_quad3_kernel       n = 3, one DPP quad per rollout (swimmer_quad3.h): 8193 .. 16384 rollouts
 //   swimmer_rollout_row.hip
@@ -140,6 +143,22 @@ constexpr int oct_packed_loop_pad() { return SW_OCTP_LOOP_PAD; }
 #define SW_OCTL_LOOP_PAD 2
 #endif
 constexpr int oct_lean_loop_pad() { return SW_OCTL_LOOP_PAD; }
+// the lean mode with the neighbour's matrix entry (rollout_octs3_kernel): other instructions in the loop again, a pad
+// of its own.  Swept over the eight even pads with sixteen steps per trip (profiles/r13_b_octs_pad_sweep.log, two
+// passes; the loop is 11288 bytes): 0.2015-0.2059 ms per launch; 2 and 10 (loop head at offset 0 and 32 of its line) are
+// the best two in both passes (0.2015-0.2023), 2 is pinned.  -DSW_OCTS_LOOP_PAD=k overrides it for a sweep
+#ifndef SW_OCTS_LOOP_PAD
+#define SW_OCTS_LOOP_PAD 2
+#endif
+constexpr int oct_next_e_loop_pad() { return SW_OCTS_LOOP_PAD; }
+// rollout_octs3_kernel alone: a main loop of sixteen steps per trip ahead of the eight-step one (eight more pinned
+// SGPRs of store offsets).  Measured in the same sweep: 0.2016 against 0.2048 ms per launch with eight steps per trip
+// (both at pad 2; that kernel's own repeats are 0.0008 apart), so it is on; 0 is the eight-step loop, for measurement.
+// (A trip counter that counts down, two scalar instructions fewer per trip, gained 0.0013 ms on the eight-step loop
+// and nothing on this one, 0.2019 against 0.2016: not kept.)
+#ifndef SW_OCTS_TRIP16
+#define SW_OCTS_TRIP16 1
+#endif
 #ifndef SW_QUAD_LOOP_PAD
 #define SW_QUAD_LOOP_PAD 0
 #endif
@@ -264,9 +283,11 @@ int validate_params(const sw_params *p)
     if (!p) return SW_ERR_NULL;
     if (p->n < 2 || p->n > SW_MAX_SEGMENTS) return SW_ERR_SEGMENTS;
     if (p->flags & ~(SW_FLAG_ROLLOUT_LANE | SW_FLAG_ROLLOUT_QUAD | SW_FLAG_MODEL_TWIN | SW_FLAG_CAPTURE_SPLIT |
-                     SW_FLAG_CAPTURE_PACKED_V1))
+                     SW_FLAG_CAPTURE_PACKED_V1 | SW_FLAG_CAPTURE_LEAN_V1))
         return SW_ERR_PARAM;
     if ((p->flags & SW_FLAG_CAPTURE_SPLIT) && (p->flags & SW_FLAG_CAPTURE_PACKED_V1)) return SW_ERR_PARAM;   // one or the other
+    if ((p->flags & SW_FLAG_CAPTURE_LEAN_V1) && (p->flags & (SW_FLAG_CAPTURE_SPLIT | SW_FLAG_CAPTURE_PACKED_V1)))
+        return SW_ERR_PARAM;   // at most one of the three
     if (!(p->l_i > 0.0) || !(p->m_i > 0.0) || !isfinite(p->l_i) || !isfinite(p->m_i) ||
         !isfinite(p->k) || !isfinite(p->h) || !isfinite(p->dir_x) || !isfinite(p->dir_y))
         return SW_ERR_PARAM;

@@ -365,6 +365,89 @@ __device__ __forceinline__ double oct3_dynamics(const Consts &C, const OctLane &
     return det;
 }
 
+// ---- the step with the NEIGHBOUR'S ENTRY (rollout_octs3_kernel, swimmer_rollout_octp3.inc with SW_OCTP_NEXT_E 1) ----
+// Every lane solves the symmetric system [[d0,a,b],[a,d1,e],[b,e,d2]] in its rotated order (i, i+1, i+2), and
+// oct3_dynamics forms all three off-diagonal entries: a = Q(i,i+1), b = Q(i,i+2), e = Q(i+1,i+2).  But Q(i+1,i+2) is
+// what lane i+1 holds as ITS a, from the same operands in the same order:
+//     e_i  = t12(i) * fma(u_{i+1}, u_{i+2}, v_{i+1} v_{i+2})          (cc12 of lane i)
+//     a_i1 = t1(i+1) * fma(u_{i+1}, u_{i+2}, v_{i+1} v_{i+2})         (cc1 of lane i+1: its u1 is u_{i+2})
+// and t12(i) = t1(i+1) is one constexpr expression of quad3_lane (asserted below).  So e = next1(a), bit for bit, NaN
+// included (no operand is commuted): two v_mov_b32_dpp instead of v_mul_f64 + v_fma_f64 + v_mul_f64, and no cc12.
+// Lane 3 (the mirror of lane 0) reads lane 1 through next1 exactly as lane 0 does; quad_perm stays inside a quad, so
+// each quad keeps to its own copy.  (cc2 = next2(cc1) and c01 = next1(c02) hold as well, but trade instruction for
+// instruction, need commuted operands and lengthen the chain: not taken.)
+// The t1 / t12 entries of quad3_lane as constant expressions: the same calls, segment by segment.
+constexpr double quad3_t1_of(int seg)
+{
+    return seg == 0 ? -6.0 * Tw<3>(1, 2) : (seg == 1 ? -6.0 * Tw<3>(2, 3) : -6.0 * Tw<3>(3, 1));
+}
+constexpr double quad3_t12_of(int seg)
+{
+    return seg == 0 ? -6.0 * Tw<3>(2, 3) : (seg == 1 ? -6.0 * Tw<3>(3, 1) : -6.0 * Tw<3>(1, 2));
+}
+static_assert(quad3_t12_of(0) == quad3_t1_of(1), "Q(1,2): segment 0's t12 is segment 1's t1");
+static_assert(quad3_t12_of(1) == quad3_t1_of(2), "Q(2,0): segment 1's t12 is segment 2's t1");
+static_assert(quad3_t12_of(2) == quad3_t1_of(0), "Q(0,1): segment 2's t12 is segment 0's t1");
+
+// oct3_geometry without cc12 (G.cc12 stays unset: oct3_dynamics_next_e does not read it); otherwise token for token.
+__device__ __forceinline__ OctGeo oct3_geometry_next_e(const OctTrig &T)
+{
+    OctGeo G;
+    const double r = T.r, z = r * r;
+    double p = fma3(T.k[0], z, T.k[1]);
+    p = fma3(p, z, T.k[2]);
+    p = fma3(p, z, T.k[3]);
+    p = fma3(p, z, T.k[4]);
+    p = fma3(p, z, T.k[5]);
+    p = fma3(p, z, T.k[6]);
+    const double X = __builtin_fma(T.selS, r, T.selC);
+    G.u = __builtin_fma(X * z, p, X);                  // sin theta on A, cos theta on B
+    G.v = dpp_row_f64<kDppRowRor8>(G.u);               // cos theta on A, sin theta on B
+    G.u1 = dpp_f64<kDppNext1>(G.u);
+    G.v1 = dpp_f64<kDppNext1>(G.v);
+    G.u2 = dpp_f64<kDppNext2>(G.u);
+    G.v2 = dpp_f64<kDppNext2>(G.v);
+    G.cc1 = __builtin_fma(G.u, G.u1, G.v * G.v1);
+    G.cc2 = __builtin_fma(G.u, G.u2, G.v * G.v2);
+    G.f1 = __builtin_fma(G.v, G.u1, -G.u * G.v1);
+    G.f2 = __builtin_fma(G.v, G.u2, -G.u * G.v2);
+    return G;
+}
+
+// oct3_dynamics with e taken from lane i+1's a; otherwise token for token.
+__device__ __forceinline__ double oct3_dynamics_next_e(const Consts &C, const OctLane &O, const OctGeo &G,
+                                                       double &Pu, double Pv, double &thd, double w1, double w2,
+                                                       double tq_scaled)
+{
+    // g~ = sigma (normal velocity of this segment's centre)
+    double g = __builtin_fma(Pv, G.v, -Pu * G.u);
+    g = __builtin_fma(O.kvw0, thd, g);
+    g = __builtin_fma(O.kvw1 * G.cc1, w1, g);
+    g = __builtin_fma(O.kvw2 * G.cc2, w2, g);
+    const double g1 = dpp_f64<kDppNext1>(g), g2 = dpp_f64<kDppNext2>(g);
+    // this quad's barycentre sum: A: sum g_j sin th_j, B: -sum g_j cos th_j
+    const double su = __builtin_fma(g2, G.u2, __builtin_fma(g1, G.u1, g * G.u));
+    double cent = __builtin_fma(O.kt1 * (w1 * w1), G.f1, tq_scaled);
+    cent = __builtin_fma(O.kt2 * (w2 * w2), G.f2, cent);
+    double fric = O.ka0 * g;
+    fric = __builtin_fma(O.ka1 * G.cc1, g1, fric);
+    fric = __builtin_fma(O.ka2 * G.cc2, g2, fric);
+    double r0 = __builtin_fma(-C.six_k_m, fric, cent);
+    r0 = __builtin_fma(C.kl_m, thd, r0);
+    const double r1 = dpp_f64<kDppNext1>(r0), r2 = dpp_f64<kDppNext2>(r0);
+    const double a = O.t1 * G.cc1, b = O.t2 * G.cc2, e = dpp_f64<kDppNext1>(a);   // Q(i+1, i+2): lane i+1's a
+    const double c00 = __builtin_fma(-e, e, O.d12);
+    const double c01 = __builtin_fma(b, e, -a * O.d2);
+    const double c02 = __builtin_fma(a, e, -b * O.d1);
+    const double det = __builtin_fma(O.d0, c00, __builtin_fma(a, c01, b * c02));
+    const double num = __builtin_fma(c00, r0, __builtin_fma(c01, r1, c02 * r2));
+    const double tdd = num * rcp_f64_1n(det);
+    // A: Gdot_x += (h k l / (n m)) sum g_j sin th_j;  B: Gdot_y -= ... sum g_j cos th_j: the same FMA
+    Pu = __builtin_fma(C.h_kl_nm, su, Pu);
+    thd = __builtin_fma(C.h, tdd, thd);
+    return det;
+}
+
 // The packed record of rollout_octp3_kernel (swimmer_rollout_octp3.inc): one value per lane of the rollout.
 // Quad A's segment lanes keep `th`; the B lanes (banks 2 and 3 of the 16-lane row) take QUAD A's thd through
 // row_ror:8 -- two v_mov_b32_dpp that leave the A lanes' halves untouched; lane 3 of either quad takes its own Pu.

@@ -90,15 +90,18 @@ rollout_octp3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__re
                      double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
 {
 #define SW_OCTP_LEAN 0
+#define SW_OCTP_NEXT_E 0
 #include "swimmer_rollout_octp3.inc"
+#undef SW_OCTP_NEXT_E
 #undef SW_OCTP_LEAN
 }
 
 // The packed record form with a leaner step (the same body with SW_OCTP_LEAN 1; its header lists the three places that
 // differ): the trajectory stores take their scalar offsets from seven loop-invariant SGPRs and the trip's base from
 // the vector offset, bumped once per trip, and the range test branches on vcc.  21 scalar instructions fewer per trip
-// of eight steps; every output has rollout_octp3_kernel's bits.  The default of a launch with capture and V2 moments;
-// SW_FLAG_CAPTURE_PACKED_V1 keeps rollout_octp3_kernel.
+// of eight steps; every output has rollout_octp3_kernel's bits.  SW_FLAG_CAPTURE_LEAN_V1 launches it (the default of
+// a launch with capture and V2 moments is rollout_octs3_kernel, below); SW_FLAG_CAPTURE_PACKED_V1 keeps
+// rollout_octp3_kernel.
 template <bool ARS>
 __global__ void __launch_bounds__(kOctBlock)
 rollout_octl3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__restrict__ policies,
@@ -109,7 +112,30 @@ rollout_octl3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__re
                      double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
 {
 #define SW_OCTP_LEAN 1
+#define SW_OCTP_NEXT_E 0
 #include "swimmer_rollout_octp3.inc"
+#undef SW_OCTP_NEXT_E
+#undef SW_OCTP_LEAN
+}
+
+// The lean kernel with the neighbour's matrix entry (the same body with SW_OCTP_NEXT_E 1): Q(i+1, i+2) of a lane's
+// rotated 3x3 system is lane i+1's Q(i, i+1), bit for bit, so a step takes it through two DPP moves and forms neither
+// cos(th_i1 - th_i2) nor its product with t12 (swimmer_oct3.h: oct3_geometry_next_e / oct3_dynamics_next_e), and its
+// main loop runs sixteen steps per trip (SW_OCTS_TRIP16).  Every output has rollout_octl3_kernel's bits.  The default of a launch with capture and V2 moments;
+// SW_FLAG_CAPTURE_LEAN_V1 keeps rollout_octl3_kernel.
+template <bool ARS>
+__global__ void __launch_bounds__(kOctBlock)
+rollout_octs3_kernel(sw::Consts C, int64_t n_roll, int32_t H, const double *__restrict__ policies,
+                     const double *__restrict__ deltas, int64_t dir_begin, double nu,
+                     const double *__restrict__ mean, const double *__restrict__ inv_std,
+                     const double *__restrict__ state0, double *__restrict__ returns,
+                     double *__restrict__ traj, double *__restrict__ final_state,
+                     double *__restrict__ moments, int32_t *__restrict__ status, SideJob side)
+{
+#define SW_OCTP_LEAN 1
+#define SW_OCTP_NEXT_E 1
+#include "swimmer_rollout_octp3.inc"
+#undef SW_OCTP_NEXT_E
 #undef SW_OCTP_LEAN
 }
 
@@ -232,15 +258,18 @@ using namespace sw_launch;
 int launch_oct3(const sw_params *p, const RolloutPlan &plan, bool ars, int64_t n_roll, int32_t H, const RolloutArgs &a,
                 hipStream_t stream, const SideWork *side)
 {
-    // capture + V2 moments: the packed record form with the lean step, unless SW_FLAG_CAPTURE_PACKED_V1 asks for the
-    // first packed kernel or SW_FLAG_CAPTURE_SPLIT for the three-store kernel
+    // capture + V2 moments: the packed record form with the lean step and the neighbour's matrix entry, unless
+    // SW_FLAG_CAPTURE_LEAN_V1 asks for the lean kernel before it, SW_FLAG_CAPTURE_PACKED_V1 for the first packed
+    // kernel or SW_FLAG_CAPTURE_SPLIT for the three-store kernel (validate_params: at most one of the three)
     if (a.traj && a.moments && !(p->flags & SW_FLAG_CAPTURE_SPLIT)) {
-        with_bools([&](auto ARS, auto V1) {
+        with_bools([&](auto ARS, auto V1, auto LEAN_V1) {
             if constexpr (V1.value)
                 launch_segment_per_lane(rollout_octp3_kernel<ARS.value>, p, plan, n_roll, H, a, stream, side);
-            else
+            else if constexpr (LEAN_V1.value)
                 launch_segment_per_lane(rollout_octl3_kernel<ARS.value>, p, plan, n_roll, H, a, stream, side);
-        }, ars, (p->flags & SW_FLAG_CAPTURE_PACKED_V1) != 0);
+            else
+                launch_segment_per_lane(rollout_octs3_kernel<ARS.value>, p, plan, n_roll, H, a, stream, side);
+        }, ars, (p->flags & SW_FLAG_CAPTURE_PACKED_V1) != 0, (p->flags & SW_FLAG_CAPTURE_LEAN_V1) != 0);
         return launch_status();
     }
     with_bools([&](auto ARS, auto TRAJ, auto MOM) {

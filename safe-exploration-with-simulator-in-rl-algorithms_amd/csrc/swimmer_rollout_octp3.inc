@@ -1,4 +1,4 @@
-// Body of rollout_octp3_kernel and rollout_octl3_kernel (csrc/swimmer_rollout_n3.hip): the mirror-quad rollout of
+// Body of rollout_octp3_kernel, rollout_octl3_kernel and rollout_octs3_kernel (csrc/swimmer_rollout_n3.hip): the mirror-quad rollout of
 // swimmer_rollout_oct3.inc with trajectory capture AND V2 moment sums, in the PACKED record form.  Included INSIDE the
 // kernel's braces, with SW_OCTP_LEAN defined as 0 (rollout_octp3_kernel) or 1 (rollout_octl3_kernel: same record, same
 // arithmetic, less scalar bookkeeping per step -- below, after the note on the two files).
@@ -40,8 +40,24 @@
 //      s_cbranch_vccnz reaches the same out-of-line re-normalisation block; no s_cmp_lg_u64.
 // Everything else (lane roles, Z, X = Z - shift, m1, m2, octp3_pack, the epilogue, the riding covariance tile) is one
 // text for both kernels; tests/test_lean_capture_gpu.py compares their outputs bit for bit.
+//
+// SW_OCTP_NEXT_E (0 or 1; 1 only together with SW_OCTP_LEAN 1: rollout_octs3_kernel) switches the step itself, in the
+// places marked `#if SW_OCTP_NEXT_E`; with 0 the text the compiler sees is the lean kernel's as it was, and its machine
+// code is pinned as well (tests/test_lean_capture_isa.py):
+//   1. the geometry: oct3_geometry_next_e forms no cos(th_i1 - th_i2);
+//   2. the dynamics: oct3_dynamics_next_e takes the matrix entry Q(i+1, i+2) from lane i+1, whose Q(i, i+1) it is
+//      (swimmer_oct3.h has the identity and its static_asserts): two DPP moves for three f64 instructions;
+//   3. the loop: a pad of its own (oct_next_e_loop_pad()) and, with SW_OCTS_TRIP16 (swimmer_launch.h: on), a main loop
+//      of sixteen steps per trip ahead of the eight-step one, with eight more pinned store offsets k8..k15.
+// tests/test_neighbour_entry_gpu.py compares its outputs with the other three kernels', bit for bit.
 #ifndef SW_OCTP_LEAN
 #error "define SW_OCTP_LEAN as 0 or 1 before including swimmer_rollout_octp3.inc"
+#endif
+#ifndef SW_OCTP_NEXT_E
+#error "define SW_OCTP_NEXT_E as 0 or 1 before including swimmer_rollout_octp3.inc"
+#endif
+#if SW_OCTP_NEXT_E && !SW_OCTP_LEAN
+#error "SW_OCTP_NEXT_E is a variant of the lean mode"
 #endif
     side_flag(side);
     if (blockIdx.x >= side.first_cov_block) {   // a covariance workgroup riding along (uniform)
@@ -96,6 +112,12 @@
     uint32_t bump8 = 8 * slab, bump4 = 4 * slab, bump2 = 2 * slab;
     asm volatile("" : "+s"(k1), "+s"(k2), "+s"(k3), "+s"(k4), "+s"(k5), "+s"(k6), "+s"(k7));
     asm volatile("" : "+s"(bump8), "+s"(bump4), "+s"(bump2));
+#if SW_OCTP_NEXT_E && SW_OCTS_TRIP16
+    uint32_t k8 = 8 * slab, k9 = 9 * slab, k10 = 10 * slab, k11 = 11 * slab, k12 = 12 * slab, k13 = 13 * slab,
+             k14 = 14 * slab, k15 = 15 * slab, bump16 = 16 * slab;
+    asm volatile("" : "+s"(k8), "+s"(k9), "+s"(k10), "+s"(k11), "+s"(k12), "+s"(k13), "+s"(k14), "+s"(k15),
+                 "+s"(bump16));
+#endif
 #define SW_OCTP_STEP_AT(K) soff = (K)
 #define SW_OCTP_TRIP_END(BUMP) vrun += (BUMP)
     auto store_cell = [&](double v) {
@@ -128,7 +150,11 @@
     Th = __builtin_fma(V[4], sw::dpp_f64<sw::kDppNext1>(th), Th);
     Th = __builtin_fma(V[6], sw::dpp_f64<sw::kDppNext2>(th), Th);
     const double hV2 = C.h * V[2], hV4 = C.h * V[4], hV6 = C.h * V[6];
+#if SW_OCTP_NEXT_E
+    sw::OctGeo G = sw::oct3_geometry_next_e(A), Gn;
+#else
     sw::OctGeo G = sw::oct3_geometry(A), Gn;
+#endif
     double magic = 6755399441055744.0;   // 1.5 * 2^52, pinned in a VGPR pair for oct3_keep_reduced
     asm volatile("" : "+v"(magic));
     auto one_step = [&](const sw::OctGeo &Gc, sw::OctGeo &Gx) {
@@ -153,8 +179,13 @@
 #else
         sw::oct3_keep_reduced(A, thmax, magic, designation, outside);   // untaken branch; rare re-normalisation
 #endif
+#if SW_OCTP_NEXT_E
+        Gx = sw::oct3_geometry_next_e(A);
+        det = sw::oct3_dynamics_next_e(C, O, Gc, Pu, Pv, thd, w1, w2, tq);
+#else
         Gx = sw::oct3_geometry(A);
         det = sw::oct3_dynamics(C, O, Gc, Pu, Pv, thd, w1, w2, tq);
+#endif
         // the record: theta_{t+1} straight into Z (the angle itself is not carried in the loop), quad A's new
         // thetadot onto the B lanes (row_ror:8 under bank mask 0xc: lanes 8..15 of a row), Gdot onto lane 3
         const double Z = sw::octp3_pack(__builtin_fma(A.kd, sw::kPio2Hi, A.r), thd, Pu, lane3);
@@ -171,7 +202,33 @@
     };
     // the geometry ping-pongs between G and Gn (no register copies): an even number of steps per trip
     int32_t t = 0;
+#if SW_OCTP_NEXT_E
+    SW_PIN_LOOP(oct_next_e_loop_pad());
+#else
     SW_PIN_LOOP(SW_OCTP_LEAN ? oct_lean_loop_pad() : oct_packed_loop_pad());
+#endif
+#if SW_OCTP_NEXT_E && SW_OCTS_TRIP16
+    // sixteen steps per trip first (the eight-step loop below then runs at most once): measured -1.6 % on the launch
+    for (; t + 16 <= H; t += 16) {
+        SW_OCTP_STEP_AT(0);   one_step(G, Gn);
+        SW_OCTP_STEP_AT(k1);  one_step(Gn, G);
+        SW_OCTP_STEP_AT(k2);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k3);  one_step(Gn, G);
+        SW_OCTP_STEP_AT(k4);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k5);  one_step(Gn, G);
+        SW_OCTP_STEP_AT(k6);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k7);  one_step(Gn, G);
+        SW_OCTP_STEP_AT(k8);  one_step(G, Gn);
+        SW_OCTP_STEP_AT(k9);  one_step(Gn, G);
+        SW_OCTP_STEP_AT(k10); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k11); one_step(Gn, G);
+        SW_OCTP_STEP_AT(k12); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k13); one_step(Gn, G);
+        SW_OCTP_STEP_AT(k14); one_step(G, Gn);
+        SW_OCTP_STEP_AT(k15); one_step(Gn, G);
+        SW_OCTP_TRIP_END(bump16);
+    }
+#endif
     // eight steps per trip, as in rollout_oct3_kernel (the back edge costs a lone wave ~8-13 ns)
     for (; t + 8 <= H; t += 8) {
         SW_OCTP_STEP_AT(0);  one_step(G, Gn);

@@ -1,7 +1,8 @@
 """Rollout launch time and iteration time of the headline ARS V2 iteration (n = 3, capture + V2 moments, full covariance
-riding along) in the packed record form ("auto": with the lean step, rollout_octl3_kernel; "packed_v1": the first packed
-kernel, rollout_octp3_kernel) and the three-store form ("split"), through the native pipeline.  For the loop-placement
-sweeps of the packed kernels (SWIMMER_HIP_LIB=... over builds with -DSW_OCTP_LOOP_PAD=k / -DSW_OCTL_LOOP_PAD=k,
+riding along) in the packed record form ("auto": the lean step with the neighbour's matrix entry, rollout_octs3_kernel;
+"lean_v1": the lean step before it, rollout_octl3_kernel; "packed_v1": the first packed kernel, rollout_octp3_kernel)
+and the three-store form ("split"), through the native pipeline.  For the loop-placement sweeps of the packed kernels
+(SWIMMER_HIP_LIB=... over builds with -DSW_OCTP_LOOP_PAD=k / -DSW_OCTL_LOOP_PAD=k / -DSW_OCTS_LOOP_PAD=k,
 scripts/ab_probe.sh) and as a same-process cross-check of the forms.  PK=auto,split chooses the forms (default; a
 library from before the lean step knows "auto" and "split" only), PREPS the number of timed blocks of 50 iterations
 per form (interleaved).  Design aid."""
