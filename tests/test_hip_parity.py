@@ -317,7 +317,8 @@ def test_rollout_batch_vs_oracle_and_moments(sw, kernel):
         assert np.abs(ret2.cpu().numpy() - np.array(ref2)).max() <= 1e-9
 
 
-@pytest.mark.parametrize("n,R,H", [(3, 200, 333), (6, 70, 257), (6, 4096, 130), (7, 129, 300), (8, 65, 131)])
+@pytest.mark.parametrize("n,R,H", [(3, 200, 333), (6, 70, 257), (6, 4096, 130), (7, 129, 300), (8, 65, 131),
+                                   (2, 70, 257), (4, 129, 130), (5, 65, 131)])     # traj_moments_kernel<D>: every D
 def test_covariance_pass_on_ragged_tiles(sw, n, R, H):
     """sw_traj_moments_f64 (np.mean / np.cov over the saved states, ars_agent.py:180-182) on sizes
     that do not divide its tiles: partial last column tile, partial last step tile, an odd number
