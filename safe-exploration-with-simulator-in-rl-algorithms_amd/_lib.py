@@ -238,7 +238,8 @@ def check(rc, what):
 
 
 def ptr(t):
-    """Device pointer of a contiguous float64 / int32 CUDA tensor, or NULL for None."""
+    """Device pointer of a contiguous CUDA tensor, or NULL for None.  It looks at nothing else: dtype, shape and
+    which GPU are checked by the wrappers of kernels.py, which name the parameter when they refuse one."""
     if t is None:
         return None
     if not t.is_cuda or not t.is_contiguous():

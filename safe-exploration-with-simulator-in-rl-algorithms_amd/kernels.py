@@ -3,30 +3,99 @@
 Shapes follow the ABI: states are SoA [d, n_env], actions [m, n_env], policies AoS
 [n_roll, m, d], trajectories [H, d, n_roll].  Everything is float64 and stays on the GPU;
 all calls are asynchronous on torch's current stream.
+
+Every tensor a wrapper hands to the library goes through ONE check first (`_tensor`, with `_opt` for an argument that
+may be None and `_out` for an output that is allocated when None): dtype, exact shape (or a lower bound where the ABI
+has one), contiguity, and the device of the call's first required tensor, which must be a GPU.  A miss is a
+SwimmerHipError that names the parameter, what was expected and what was given, before anything is launched.  The
+one exception are the pre-bound hot paths, whose buffers are their owner's, allocated once: StepPlan.launch (its
+constructor checks, once), SingleEnv (no tensors at all) and ArsPipeline.rollouts / ArsPipeline.update.
 """
 import ctypes
 
 import torch
 
 from . import _lib
-from ._lib import SwParams, check, load, ptr, require_gpu, stream_ptr
+from ._lib import SwParams, SwimmerHipError, check, load, ptr, require_gpu, stream_ptr
+
+_I32 = torch.int32
 
 
-def _f64(shape, device):
-    return torch.empty(shape, dtype=torch.float64, device=device)
+class _Min(int):
+    """A shape entry that is a lower bound on the size, not the size."""
+
+    def __repr__(self):
+        return f">={int(self)}"
 
 
-def _want(t, name, shape):
-    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape):
-        raise _lib.SwimmerHipError(f"{name}: expected float64 tensor of shape {tuple(shape)}, "
-                                   f"got {t.dtype} {tuple(t.shape)}")
-    return t
+_ANY = _Min(0)
+
+
+def _describe(t):
+    if not isinstance(t, torch.Tensor):
+        return "None" if t is None else type(t).__name__
+    return f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else ", not contiguous")
+
+
+def _tensor(t, name, shape, on, dtype=torch.float64):
+    """The argument check of every wrapper: `t` is a contiguous `dtype` tensor of `shape` (a tuple; _Min entries are
+    lower bounds) on the call's device: `on` = (device, the parameter that set it).  -> t, or SwimmerHipError."""
+    if (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == on[0] and t.is_contiguous()
+            and (t.shape == shape or (len(t.shape) == len(shape) and all(
+                g >= w if isinstance(w, _Min) else g == w for g, w in zip(t.shape, shape))))):
+        return t
+    raise SwimmerHipError(f"{name}: expected a contiguous {dtype} tensor of shape {shape} on {on[0]} "
+                          f"as {on[1]}, got {_describe(t)}")
+
+
+def _opt(t, name, shape, on, dtype=torch.float64):
+    """_tensor for an argument that may be None."""
+    return None if t is None else _tensor(t, name, shape, on, dtype)
+
+
+def _out(t, name, shape, on, dtype=torch.float64, fill=None):
+    """_tensor for an output; None: a new tensor, uninitialised or filled with `fill`."""
+    if t is not None:
+        return _tensor(t, name, shape, on, dtype)
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=on[0])
+    return torch.full(shape, fill, dtype=dtype, device=on[0])
+
+
+def _gpu(t, name, ndim):
+    """The `on` of a call whose first required tensor is `t` ([ndim]-dimensional, so that the call's sizes can be
+    read off it before its own check): its device, which must be a GPU."""
+    device = t.device if isinstance(t, torch.Tensor) else None
+    if device is None or device.type != "cuda" or t.dim() != ndim:
+        raise SwimmerHipError(f"{name}: expected a {ndim}-D tensor on the GPU, got {_describe(t)}")
+    return device, name
+
+
+def _pair(mean, inv_std, shape, on, required=False):
+    """mean and inv_std: both or neither (both when `required`)."""
+    need = _tensor if required or mean is not None or inv_std is not None else _opt
+    need(mean, "mean", shape, on)
+    need(inv_std, "inv_std", shape, on)
+
+
+def _transitions(p, state, action, *next_ref):
+    """(d, T, on) of the SoA columns state [d, T], action [m, T] and, where there is one, next_ref [d, T]."""
+    on = _gpu(state, "state", 2)
+    d, T = p.d, state.shape[1]
+    _tensor(state, "state", (d, T), on)
+    _tensor(action, "action", (p.m, T), on)
+    for t in next_ref:
+        _tensor(t, "next_ref", (d, T), on)
+    return d, T, on
 
 
 def reset(p: SwParams, n_env: int, device="cuda:0", out=None):
     """SwimmerEnv.reset for n_env swimmers -> state [d, n_env]."""
     require_gpu()
-    state = _f64((p.d, n_env), device) if out is None else _want(out, "out", (p.d, n_env))
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    state = _out(out, "out", (p.d, n_env), (device, "device"))
     check(load().sw_reset_f64(ctypes.byref(p), n_env, ptr(state), stream_ptr()), "sw_reset_f64")
     return state
 
@@ -34,11 +103,10 @@ def reset(p: SwParams, n_env: int, device="cuda:0", out=None):
 def step(p: SwParams, state, action, out=None, reward=None, status=None):
     """One physics step.  Returns (next_state [d, n_env], reward [n_env])."""
     require_gpu()
-    n_env = state.shape[1]
-    _want(state, "state", (p.d, n_env))
-    _want(action, "action", (p.m, n_env))
-    out = _f64((p.d, n_env), state.device) if out is None else _want(out, "out", (p.d, n_env))
-    reward = _f64((n_env,), state.device) if reward is None else _want(reward, "reward", (n_env,))
+    d, n_env, on = _transitions(p, state, action)
+    out = _out(out, "out", (d, n_env), on)
+    reward = _out(reward, "reward", (n_env,), on)
+    _opt(status, "status", (n_env,), on, _I32)
     check(load().sw_step_f64(ctypes.byref(p), n_env, ptr(state), ptr(action), ptr(out),
                              ptr(reward), ptr(status), stream_ptr()), "sw_step_f64")
     return out, reward
@@ -53,12 +121,8 @@ def step_residual(p: SwParams, state, action, next_ref, partial=None):
     || step(state, action) - next_ref ||_2 over the transitions (SoA [d, T], [m, T], [d, T]); their sum is I(x).
     The simulated next states are never written (sw_step_residual_f64)."""
     require_gpu()
-    T = state.shape[1]
-    _want(state, "state", (p.d, T))
-    _want(action, "action", (p.m, T))
-    _want(next_ref, "next_ref", (p.d, T))
-    nb = int(load().sw_step_residual_blocks(T))
-    partial = _f64((nb,), state.device) if partial is None else _want(partial, "partial", (nb,))
+    _, T, on = _transitions(p, state, action, next_ref)
+    partial = _out(partial, "partial", (step_residual_blocks(T),), on)
     check(load().sw_step_residual_f64(ctypes.byref(p), T, ptr(state), ptr(action), ptr(next_ref), ptr(partial),
                                       stream_ptr()), "sw_step_residual_f64")
     return partial
@@ -71,49 +135,22 @@ def step_residual_population(p_base: SwParams, cand, state, action, next_ref, pa
     bits step_residual gives for candidate j, value[j] is its fixed-order sum, status[j] is SW_STATUS_PARAM (8) for
     a candidate with non-positive / non-finite l_i, m_i or non-finite k (NaN partials and value), else 0."""
     require_gpu()
-    T = state.shape[1]
-    _want(state, "state", (p_base.d, T))
-    _want(action, "action", (p_base.m, T))
-    _want(next_ref, "next_ref", (p_base.d, T))
-    if cand.dim() != 2 or cand.shape[0] < 1:
-        raise _lib.SwimmerHipError(f"cand: expected float64 tensor of shape (n_cand, 3), got {tuple(cand.shape)}")
-    n_cand = cand.shape[0]
-    _want(cand, "cand", (n_cand, 3))
-    if not cand.is_contiguous():
-        raise _lib.SwimmerHipError("cand: expected a contiguous tensor")
-    nb = int(load().sw_step_residual_blocks(T))
-    partial = _f64((n_cand, nb), state.device) if partial is None else _want(partial, "partial", (n_cand, nb))
-    if value is None:   # zeros: with T = 0 the library writes nothing and I is 0
-        value = torch.zeros((n_cand,), dtype=torch.float64, device=state.device)
-    else:
-        _want(value, "value", (n_cand,))
-    if status is None:
-        status = torch.zeros((n_cand,), dtype=torch.int32, device=state.device)
-    elif status.dtype != torch.int32 or tuple(status.shape) != (n_cand,):
-        raise _lib.SwimmerHipError(f"status: expected int32 tensor of shape ({n_cand},)")
+    _, T, on = _transitions(p_base, state, action, next_ref)
+    n_cand = _tensor(cand, "cand", (_Min(1), 3), on).shape[0]
+    partial = _out(partial, "partial", (n_cand, step_residual_blocks(T)), on)
+    value = _out(value, "value", (n_cand,), on, fill=0.0)   # zeros: with T = 0 the library writes nothing and I is 0
+    status = _out(status, "status", (n_cand,), on, _I32, fill=0)
     check(load().sw_step_residual_pop_f64(ctypes.byref(p_base), n_cand, ptr(cand), T, ptr(state), ptr(action),
                                           ptr(next_ref), ptr(partial), ptr(value), ptr(status), stream_ptr()),
           "sw_step_residual_pop_f64")
     return value, partial, status
 
 
-def _want_typed(t, name, dtype, shape):
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise _lib.SwimmerHipError(f"{name}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, "
-                                   f"got {t.dtype} {tuple(t.shape)}")
-    return t
-
-
 def _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref):
-    T = state.shape[1]
-    _want(state, "state", (p_base.d, T))
-    _want(action, "action", (p_base.m, T))
-    _want(next_ref, "next_ref", (p_base.d, T))
-    if set_begin.dim() != 1 or set_begin.shape[0] < 2:
-        raise _lib.SwimmerHipError(f"set_begin: expected int64 tensor of shape (n_set + 1,), got {tuple(set_begin.shape)}")
-    n_set = set_begin.shape[0] - 1
-    _want_typed(set_begin, "set_begin", torch.int64, (n_set + 1,))
-    return T, n_set, int(load().sw_step_residual_blocks(int(max_set_len)))
+    """(T, n_set, blocks of the longest set, on) of transitions cut into sets by set_begin (int64 [n_set + 1])."""
+    _, T, on = _transitions(p_base, state, action, next_ref)
+    n_set = _tensor(set_begin, "set_begin", (_Min(2),), on, torch.int64).shape[0] - 1
+    return T, n_set, step_residual_blocks(max_set_len), on
 
 
 def step_residual_sets(p_base: SwParams, set_begin, max_set_len: int, cand, cand_set, state, action, next_ref,
@@ -126,18 +163,12 @@ def step_residual_sets(p_base: SwParams, set_begin, max_set_len: int, cand, cand
     partial[j] have the bits step_residual gives for candidate j on its set's slice (the rest is not written),
     value[j] is their fixed-order sum."""
     require_gpu()
-    T, n_set, nb = _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref)
-    if cand.dim() != 2 or cand.shape[0] < 1:
-        raise _lib.SwimmerHipError(f"cand: expected float64 tensor of shape (n_cand, 3), got {tuple(cand.shape)}")
-    n_cand = cand.shape[0]
-    _want_typed(cand, "cand", torch.float64, (n_cand, 3))
-    _want_typed(cand_set, "cand_set", torch.int32, (n_cand,))
-    partial = _f64((n_cand, nb), state.device) if partial is None else _want(partial, "partial", (n_cand, nb))
-    value = _f64((n_cand,), state.device) if value is None else _want(value, "value", (n_cand,))
-    if status is None:
-        status = torch.zeros((n_cand,), dtype=torch.int32, device=state.device)
-    else:
-        _want_typed(status, "status", torch.int32, (n_cand,))
+    T, n_set, nb, on = _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref)
+    n_cand = _tensor(cand, "cand", (_Min(1), 3), on).shape[0]
+    _tensor(cand_set, "cand_set", (n_cand,), on, _I32)
+    partial = _out(partial, "partial", (n_cand, nb), on)
+    value = _out(value, "value", (n_cand,), on)
+    status = _out(status, "status", (n_cand,), on, _I32, fill=0)
     check(load().sw_step_residual_sets_f64(ctypes.byref(p_base), n_set, ptr(set_begin), int(max_set_len), n_cand,
                                            ptr(cand), ptr(cand_set), T, ptr(state), ptr(action), ptr(next_ref),
                                            ptr(partial), ptr(value), ptr(status), stream_ptr()),
@@ -153,23 +184,14 @@ def step_residual_normal_sets(p_base: SwParams, set_begin, max_set_len: int, poi
     J by central differences.  active (int32 [n_set]): sets with 0 are neither read nor written.  Returns (out,
     status [n_set])."""
     require_gpu()
-    T, n_set, nb = _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref)
-    if points.dim() != 3:
-        raise _lib.SwimmerHipError(f"points: expected float64 tensor of shape (n_set, n_point, 3), got "
-                                   f"{tuple(points.shape)}")
-    n_point = points.shape[1]
-    _want_typed(points, "points", torch.float64, (n_set, n_point, 3))
+    T, n_set, nb, on = _sets_shapes(p_base, set_begin, max_set_len, state, action, next_ref)
+    n_point = _tensor(points, "points", (n_set, _ANY, 3), on).shape[1]
     K = 13 if n_point == 7 else 1
-    if inv_2e is not None:
-        _want_typed(inv_2e, "inv_2e", torch.float64, (n_set, 3))
-    if active is not None:
-        _want_typed(active, "active", torch.int32, (n_set,))
-    partial = _f64((n_set, K, nb), state.device) if partial is None else _want(partial, "partial", (n_set, K, nb))
-    out = _f64((n_set, K), state.device) if out is None else _want(out, "out", (n_set, K))
-    if status is None:
-        status = torch.zeros((n_set,), dtype=torch.int32, device=state.device)
-    else:
-        _want_typed(status, "status", torch.int32, (n_set,))
+    _opt(inv_2e, "inv_2e", (n_set, 3), on)
+    _opt(active, "active", (n_set,), on, _I32)
+    partial = _out(partial, "partial", (n_set, K, nb), on)
+    out = _out(out, "out", (n_set, K), on)
+    status = _out(status, "status", (n_set,), on, _I32, fill=0)
     check(load().sw_step_residual_normal_sets_f64(ctypes.byref(p_base), n_set, ptr(set_begin), int(max_set_len),
                                                   n_point, ptr(points), ptr(inv_2e), ptr(active), T, ptr(state),
                                                   ptr(action), ptr(next_ref), ptr(partial), ptr(out), ptr(status),
@@ -180,16 +202,15 @@ def step_residual_normal_sets(p_base: SwParams, set_begin, max_set_len: int, poi
 class StepPlan(object):
     """A pre-bound sw_step_f64 launch: all argument conversion is done once, `launch()` is a
     single foreign call (the per-launch Python overhead of `step()` is larger than the 8192-env
-    kernel itself).  Launches on the stream that was current when the plan was made."""
+    kernel itself).  Launches on the stream that was current when the plan was made.  The constructor checks the
+    tensors as step() does, once; launch() checks nothing."""
 
     def __init__(self, p: SwParams, state, action, out, reward=None, status=None):
         require_gpu()
-        n_env = state.shape[1]
-        _want(state, "state", (p.d, n_env))
-        _want(action, "action", (p.m, n_env))
-        _want(out, "out", (p.d, n_env))
-        if reward is not None:
-            _want(reward, "reward", (n_env,))
+        d, n_env, on = _transitions(p, state, action)
+        _tensor(out, "out", (d, n_env), on)
+        _opt(reward, "reward", (n_env,), on)
+        _opt(status, "status", (n_env,), on, _I32)
         self._keep = (p, state, action, out, reward, status)
         self._fn = load().sw_step_f64
         self._args = (ctypes.byref(p), n_env, ptr(state), ptr(action), ptr(out), ptr(reward),
@@ -224,8 +245,8 @@ class DirectComm(object):
             if rc:
                 why = f"sw_comm_unique_id: {_lib.ERR_NAMES.get(rc, rc)}"
         if not agree(why is None):
-            raise _lib.SwimmerHipError("direct RCCL set-up failed on " +
-                                       (f"this rank: {why}" if why else "another rank"))
+            raise SwimmerHipError("direct RCCL set-up failed on " +
+                                  (f"this rank: {why}" if why else "another rank"))
         ident = broadcast_id(bytes(buf) if rank == 0 else None)
         buf = (ctypes.c_uint8 * 128).from_buffer_copy(ident)
         h = ctypes.c_void_p()
@@ -233,18 +254,19 @@ class DirectComm(object):
         if not agree(rc == 0):
             if rc == 0:
                 lib.sw_comm_destroy(h)
-            raise _lib.SwimmerHipError("sw_comm_create failed on " +
-                                       (f"this rank: {_lib.ERR_NAMES.get(rc, rc)}" if rc else "another rank"))
+            raise SwimmerHipError("sw_comm_create failed on " +
+                                  (f"this rank: {_lib.ERR_NAMES.get(rc, rc)}" if rc else "another rank"))
         self._h, self._lib, self.world, self.rank = h, lib, world, rank
         self._fn = lib.sw_comm_all_gather_f64
 
     def all_gather(self, send, gathered):
         """gathered[r * L : (r + 1) * L] <- rank r's send (L = send.numel()), on the current stream."""
-        if gathered.numel() != self.world * send.numel():
-            raise _lib.SwimmerHipError("all_gather: gathered must hold world x send doubles")
-        rc = self._fn(self._h, ptr(send), ptr(gathered), send.numel(), stream_ptr())
+        on = _gpu(send, "send", 1)
+        L = _tensor(send, "send", (_ANY,), on).shape[0]
+        _tensor(gathered, "gathered", (self.world * L,), on)
+        rc = self._fn(self._h, ptr(send), ptr(gathered), L, stream_ptr())
         if rc:
-            raise _lib.SwimmerHipError("sw_comm_all_gather_f64: " + self._lib.sw_comm_last_error(self._h).decode())
+            raise SwimmerHipError("sw_comm_all_gather_f64: " + self._lib.sw_comm_last_error(self._h).decode())
         return gathered
 
     def close(self):
@@ -263,7 +285,8 @@ class SingleEnv(object):
     """sw_env1: ONE swimmer handed over in host memory -- the batch-1 surface under
     `SwimmerEnv.step` (remy_swimmer_env.py:41-56).  The handle owns a pinned, device-mapped I/O
     block; `io` is a NumPy view of it (offsets SW_ENV1_* of include/swimmer_hip.h).  A step is
-    one kernel launch and one host wait: no tensor is created, nothing is copied by a call."""
+    one kernel launch and one host wait: no tensor is created, nothing is copied by a call, and there is no
+    tensor argument to check."""
     STATE, ACTION, NEXT, REWARD, GDD, TDD, DOUBLES = 0, 18, 32, 50, 52, 54, 64
 
     def __init__(self):
@@ -305,11 +328,9 @@ class SingleEnv(object):
 def accelerations(p: SwParams, state, action):
     """SwimmerEnv.compute_accelerations -> (Gdd [2, n_env], thdd [n, n_env])."""
     require_gpu()
-    n_env = state.shape[1]
-    _want(state, "state", (p.d, n_env))
-    _want(action, "action", (p.m, n_env))
-    gdd = _f64((2, n_env), state.device)
-    tdd = _f64((p.n, n_env), state.device)
+    _, n_env, on = _transitions(p, state, action)
+    gdd = _out(None, "gdd", (2, n_env), on)
+    tdd = _out(None, "tdd", (p.n, n_env), on)
     check(load().sw_accel_f64(ctypes.byref(p), n_env, ptr(state), ptr(action), ptr(gdd),
                               ptr(tdd), stream_ptr()), "sw_accel_f64")
     return gdd, tdd
@@ -324,23 +345,16 @@ def rollout(p: SwParams, H: int, policies, mean=None, inv_std=None, state0=None,
     """n_roll H-step rollouts, one linear policy each.  Optional output buffers are filled
     when given (see include/swimmer_hip.h for their shapes).  Returns `returns` [n_roll]."""
     require_gpu()
-    n_roll = policies.shape[0]
-    _want(policies, "policies", (n_roll, p.m, p.d))
-    dev = policies.device
-    if (mean is None) != (inv_std is None):
-        raise _lib.SwimmerHipError("mean and inv_std must be given together")
-    if mean is not None:
-        _want(mean, "mean", (p.d,))
-        _want(inv_std, "inv_std", (p.d,))
-    if state0 is not None:
-        _want(state0, "state0", (p.d, n_roll))
-    if traj is not None:
-        _want(traj, "traj", (H, p.d, n_roll))
-    if final_state is not None:
-        _want(final_state, "final_state", (p.d, n_roll))
+    on = _gpu(policies, "policies", 3)
+    n_roll = _tensor(policies, "policies", (_ANY, p.m, p.d), on).shape[0]
+    _pair(mean, inv_std, (p.d,), on)
+    _opt(state0, "state0", (p.d, n_roll), on)
+    _opt(traj, "traj", (H, p.d, n_roll), on)
+    _opt(final_state, "final_state", (p.d, n_roll), on)
     if moments is not None:
-        _want(moments, "moments", (moments_blocks(n_roll), 2 * p.d))
-    returns = _f64((n_roll,), dev) if returns is None else _want(returns, "returns", (n_roll,))
+        _tensor(moments, "moments", (moments_blocks(n_roll), 2 * p.d), on)
+    _opt(status, "status", (n_roll,), on, _I32)
+    returns = _out(returns, "returns", (n_roll,), on)
     check(load().sw_rollout_f64(ctypes.byref(p), n_roll, H, ptr(policies), ptr(mean),
                                 ptr(inv_std), ptr(state0), ptr(returns), ptr(traj),
                                 ptr(final_state), ptr(moments), ptr(status), stream_ptr()),
@@ -355,15 +369,12 @@ def safe_rollouts(p_real: SwParams, p_sim: SwParams, H: int, policies, cost_kind
     steps from the reset state, every real step gated by the one-step simulator look-ahead (`isSafe`, :111-122).
     policies [n_roll, m, d]; optional outputs: traj [H, d, n_roll], first_refused / violations / status [n_roll] int32."""
     require_gpu()
-    n_roll = policies.shape[0]
-    _want(policies, "policies", (n_roll, p_real.m, p_real.d))
-    dev = policies.device
-    if traj is not None:
-        _want(traj, "traj", (H, p_real.d, n_roll))
+    on = _gpu(policies, "policies", 3)
+    n_roll = _tensor(policies, "policies", (_ANY, p_real.m, p_real.d), on).shape[0]
+    _opt(traj, "traj", (H, p_real.d, n_roll), on)
     for name, t in (("first_refused", first_refused), ("violations", violations), ("status", status)):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n_roll,)):
-            raise _lib.SwimmerHipError(f"{name}: expected int32 tensor of shape ({n_roll},)")
-    returns = _f64((n_roll,), dev) if returns is None else _want(returns, "returns", (n_roll,))
+        _opt(t, name, (n_roll,), on, _I32)
+    returns = _out(returns, "returns", (n_roll,), on)
     check(load().sw_safe_rollouts_f64(ctypes.byref(p_real), ctypes.byref(p_sim), n_roll, H, ptr(policies),
                                       int(cost_kind), int(cost_index), float(sim_thresh), float(real_thresh),
                                       ptr(returns), ptr(traj), ptr(first_refused), ptr(violations), ptr(status),
@@ -371,23 +382,26 @@ def safe_rollouts(p_real: SwParams, p_sim: SwParams, H: int, policies, cost_kind
     return returns
 
 
+def _ars_shapes(p, policy, deltas, dir_begin, n_dir, mean, inv_std):
+    """(n_roll, on) of the 2 n_dir rollouts of policy [m, d] along deltas [>= dir_begin + n_dir, m, d], checked with
+    mean / inv_std [d]."""
+    on = _gpu(policy, "policy", 2)
+    _tensor(policy, "policy", (p.m, p.d), on)
+    _tensor(deltas, "deltas", (_Min(dir_begin + n_dir), p.m, p.d), on)
+    _pair(mean, inv_std, (p.d,), on)
+    return 2 * n_dir, on
+
+
 def ars_rollouts(p: SwParams, H: int, policy, deltas, nu: float, dir_begin: int, n_dir: int,
                  mean=None, inv_std=None, returns=None, traj=None, moments=None, status=None):
     """The 2*n_dir exploration rollouts P +- nu*delta_i, i in [dir_begin, dir_begin+n_dir)."""
     require_gpu()
-    _want(policy, "policy", (p.m, p.d))
-    if deltas.dim() != 3 or deltas.shape[0] < dir_begin + n_dir:
-        raise _lib.SwimmerHipError("deltas: need [>= dir_begin + n_dir, m, d]")
-    _want(deltas, "deltas", (deltas.shape[0], p.m, p.d))
-    dev = policy.device
-    n_roll = 2 * n_dir
-    if (mean is None) != (inv_std is None):
-        raise _lib.SwimmerHipError("mean and inv_std must be given together")
-    if traj is not None:
-        _want(traj, "traj", (H, p.d, n_roll))
+    n_roll, on = _ars_shapes(p, policy, deltas, dir_begin, n_dir, mean, inv_std)
+    _opt(traj, "traj", (H, p.d, n_roll), on)
     if moments is not None:
-        _want(moments, "moments", (moments_blocks(n_roll), 2 * p.d))
-    returns = _f64((n_roll,), dev) if returns is None else _want(returns, "returns", (n_roll,))
+        _tensor(moments, "moments", (moments_blocks(n_roll), 2 * p.d), on)
+    _opt(status, "status", (n_roll,), on, _I32)
+    returns = _out(returns, "returns", (n_roll,), on)
     check(load().sw_ars_rollouts_f64(ctypes.byref(p), dir_begin, n_dir, H, ptr(policy),
                                      ptr(deltas), float(nu), ptr(mean), ptr(inv_std),
                                      ptr(returns), ptr(traj), ptr(moments), ptr(status),
@@ -403,30 +417,38 @@ def ars_gate(p_sim: SwParams, H: int, policy, deltas, nu: float, dir_begin: int,
     ([2*n_dir], optional) receive the simulator returns / status codes as ars_rollouts writes them; `admit`
     (optional) is an int32 [n_dir] tensor to write the flags into instead of a new one."""
     require_gpu()
-    _want(policy, "policy", (p_sim.m, p_sim.d))
-    if deltas.dim() != 3 or deltas.shape[0] < dir_begin + n_dir:
-        raise _lib.SwimmerHipError("deltas: need [>= dir_begin + n_dir, m, d]")
-    _want(deltas, "deltas", (deltas.shape[0], p_sim.m, p_sim.d))
-    dev = policy.device
-    n_roll = 2 * n_dir
-    if (mean is None) != (inv_std is None):
-        raise _lib.SwimmerHipError("mean and inv_std must be given together")
-    if mean is not None:
-        _want(mean, "mean", (p_sim.d,))
-        _want(inv_std, "inv_std", (p_sim.d,))
-    if returns is not None:
-        _want(returns, "returns", (n_roll,))
-    if status is not None and (status.dtype != torch.int32 or tuple(status.shape) != (n_roll,)
-                               or status.device != dev):
-        raise _lib.SwimmerHipError(f"status: expected int32 tensor of shape ({n_roll},) on {dev}")
-    if admit is None:
-        admit = torch.empty(n_dir, dtype=torch.int32, device=dev)
-    elif admit.dtype != torch.int32 or tuple(admit.shape) != (n_dir,) or admit.device != dev:
-        raise _lib.SwimmerHipError(f"admit: expected int32 tensor of shape ({n_dir},) on {dev}")
+    n_roll, on = _ars_shapes(p_sim, policy, deltas, dir_begin, n_dir, mean, inv_std)
+    _opt(returns, "returns", (n_roll,), on)
+    _opt(status, "status", (n_roll,), on, _I32)
+    admit = _out(admit, "admit", (n_dir,), on, _I32)
     check(load().sw_ars_gate_f64(ctypes.byref(p_sim), dir_begin, n_dir, H, ptr(policy), ptr(deltas),
                                  float(nu), ptr(mean), ptr(inv_std), float(sim_thresh), ptr(admit),
                                  ptr(returns), ptr(status), stream_ptr()), "sw_ars_gate_f64")
     return admit
+
+
+def _update_state(p, lead, on, policy, running, mean, inv_std, sigma_out):
+    """The tensors an ARS update changes, behind the agent dimensions `lead` (() for one agent): policy; running,
+    with mean and inv_std required next to it; sigma_out."""
+    _tensor(policy, "policy", lead + (p.m, p.d), on)
+    _opt(running, "running", lead + (1 + 2 * p.d,), on)
+    _pair(mean, inv_std, lead + (p.d,), on, required=running is not None)
+    _opt(sigma_out, "sigma_out", lead or (1,), on)
+
+
+def _update_moments(p, lead, on, moments, running, min_rows=0):
+    """moments [rows >= min_rows, 2d] behind `lead`, required next to running -> the rows the update reads (none
+    without running)."""
+    if running is None:
+        _opt(moments, "moments", lead + (_ANY, 2 * p.d), on)
+        return 0
+    return _tensor(moments, "moments", lead + (_Min(min_rows), 2 * p.d), on).shape[-2]
+
+
+def _update_shapes(p, on, n_dir, deltas, policy, running, mean, inv_std, sigma_out):
+    """The single-agent update's tensors behind its returns: deltas [>= n_dir, m, d] and _update_state's."""
+    _tensor(deltas, "deltas", (_Min(n_dir), p.m, p.d), on)
+    _update_state(p, (), on, policy, running, mean, inv_std, sigma_out)
 
 
 def ars_update(p: SwParams, returns, deltas, policy, alpha: float, b: float, top_b: int = 0,
@@ -434,19 +456,11 @@ def ars_update(p: SwParams, returns, deltas, policy, alpha: float, b: float, top
                sigma_out=None):
     """In-place ARS update of `policy` (+ V2 statistics when `running` is given)."""
     require_gpu()
-    n_dir = returns.shape[0] // 2
-    _want(returns, "returns", (2 * n_dir,))
-    _want(policy, "policy", (p.m, p.d))
-    _want(deltas, "deltas", (deltas.shape[0], p.m, p.d))
-    if deltas.shape[0] < n_dir:
-        raise _lib.SwimmerHipError("deltas: fewer directions than returns")
-    n_rows = 0
-    if running is not None:
-        _want(running, "running", (1 + 2 * p.d,))
-        _want(mean, "mean", (p.d,))
-        _want(inv_std, "inv_std", (p.d,))
-        n_rows = moments.shape[0]
-        _want(moments, "moments", (n_rows, 2 * p.d))
+    on = _gpu(returns, "returns", 1)
+    n_dir = returns.numel() // 2
+    _tensor(returns, "returns", (2 * n_dir,), on)
+    _update_shapes(p, on, n_dir, deltas, policy, running, mean, inv_std, sigma_out)
+    n_rows = _update_moments(p, (), on, moments, running)
     check(load().sw_ars_update_f64(ctypes.byref(p), n_dir, ptr(returns), ptr(deltas),
                                    ptr(policy), float(alpha), float(b), int(top_b),
                                    ptr(moments), n_rows, ptr(running), int(n_new_states),
@@ -455,10 +469,13 @@ def ars_update(p: SwParams, returns, deltas, policy, alpha: float, b: float, top
     return policy
 
 
-def _want_i32(t, name, shape, device):
-    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or t.device != device:
-        raise _lib.SwimmerHipError(f"{name}: expected int32 tensor of shape {tuple(shape)} on {device}")
-    return t
+def _multi_shapes(p, policy, deltas, mean, inv_std):
+    """(S, N, on) of a multi-agent launch's policy [S, m, d] and deltas [S, N, m, d], checked with mean / inv_std."""
+    on = _gpu(policy, "policy", 3)
+    S = _tensor(policy, "policy", (_Min(1), p.m, p.d), on).shape[0]
+    N = _tensor(deltas, "deltas", (S, _Min(1), p.m, p.d), on).shape[1]
+    _pair(mean, inv_std, (S, p.d), on)
+    return S, N, on
 
 
 def ars_rollouts_multi(p: SwParams, H: int, policy, deltas, nu: float, mean=None, inv_std=None, returns=None,
@@ -468,29 +485,28 @@ def ars_rollouts_multi(p: SwParams, H: int, policy, deltas, nu: float, mean=None
     ars_rollouts gives for agent a's policy, deltas, mean and inv_std; moments ([S, moments_blocks(2N), 2d]) and
     status (int32 [S, 2N]) are filled when given, agent by agent as ars_rollouts fills them."""
     require_gpu()
-    if policy.dim() != 3 or policy.shape[0] < 1:
-        raise _lib.SwimmerHipError(f"policy: expected float64 tensor of shape (S, m, d), got {tuple(policy.shape)}")
-    S = policy.shape[0]
-    _want(policy, "policy", (S, p.m, p.d))
-    if deltas.dim() != 4 or deltas.shape[1] < 1:
-        raise _lib.SwimmerHipError(f"deltas: expected float64 tensor of shape (S, N, m, d), got {tuple(deltas.shape)}")
-    N = deltas.shape[1]
-    _want(deltas, "deltas", (S, N, p.m, p.d))
-    dev = policy.device
-    if (mean is None) != (inv_std is None):
-        raise _lib.SwimmerHipError("mean and inv_std must be given together")
-    if mean is not None:
-        _want(mean, "mean", (S, p.d))
-        _want(inv_std, "inv_std", (S, p.d))
+    S, N, on = _multi_shapes(p, policy, deltas, mean, inv_std)
     if moments is not None:
-        _want(moments, "moments", (S, moments_blocks(2 * N), 2 * p.d))
-    if status is not None:
-        _want_i32(status, "status", (S, 2 * N), dev)
-    returns = _f64((S, 2 * N), dev) if returns is None else _want(returns, "returns", (S, 2 * N))
+        _tensor(moments, "moments", (S, moments_blocks(2 * N), 2 * p.d), on)
+    _opt(status, "status", (S, 2 * N), on, _I32)
+    returns = _out(returns, "returns", (S, 2 * N), on)
     check(load().sw_ars_rollouts_multi_f64(ctypes.byref(p), S, N, H, ptr(policy), ptr(deltas), float(nu), ptr(mean),
                                            ptr(inv_std), ptr(returns), ptr(moments), ptr(status), stream_ptr()),
           "sw_ars_rollouts_multi_f64")
     return returns
+
+
+def _multi_update_shapes(p, returns, deltas, policy, moments, counted, running, mean, inv_std, sigma_out):
+    """(S, n_dir, moment rows, on) of a multi-agent update: returns [S, 2N], deltas [S, N, m, d] and _update_state's
+    behind (S,); `counted`: the moments hold at least the moments_blocks(2N) rows that N directions fill."""
+    on = _gpu(returns, "returns", 2)
+    S, n_dir = _tensor(returns, "returns", (_Min(1), _Min(2)), on).shape
+    n_dir //= 2
+    _tensor(returns, "returns", (S, 2 * n_dir), on)
+    _tensor(deltas, "deltas", (S, n_dir, p.m, p.d), on)
+    _update_state(p, (S,), on, policy, running, mean, inv_std, sigma_out)
+    min_rows = moments_blocks(2 * n_dir) if counted and running is not None else 0
+    return S, n_dir, _update_moments(p, (S,), on, moments, running, min_rows), on
 
 
 def ars_update_multi(p: SwParams, returns, deltas, policy, alpha: float, b: float, top_b: int = 0,
@@ -500,46 +516,13 @@ def ars_update_multi(p: SwParams, returns, deltas, policy, alpha: float, b: floa
     [S, N, m, d], policy [S, m, d]; with `running` ([S, 1 + 2d]) also moments [S, rows, 2d], mean and inv_std
     [S, d]; sigma_out [S] or None."""
     require_gpu()
-    if returns.dim() != 2 or returns.shape[0] < 1 or returns.shape[1] < 2 or returns.shape[1] % 2:
-        raise _lib.SwimmerHipError(f"returns: expected float64 tensor of shape (S, 2N), got {tuple(returns.shape)}")
-    S, n_dir = returns.shape[0], returns.shape[1] // 2
-    _want(returns, "returns", (S, 2 * n_dir))
-    _want(policy, "policy", (S, p.m, p.d))
-    _want(deltas, "deltas", (S, n_dir, p.m, p.d))
-    n_rows = 0
-    if running is not None:
-        _want(running, "running", (S, 1 + 2 * p.d))
-        _want(mean, "mean", (S, p.d))
-        _want(inv_std, "inv_std", (S, p.d))
-        if moments is None or moments.dim() != 3:
-            raise _lib.SwimmerHipError("moments: expected float64 tensor of shape (S, rows, 2d) next to running")
-        n_rows = moments.shape[1]
-        _want(moments, "moments", (S, n_rows, 2 * p.d))
-    if sigma_out is not None:
-        _want(sigma_out, "sigma_out", (S,))
+    S, n_dir, n_rows, _ = _multi_update_shapes(p, returns, deltas, policy, moments, False, running, mean, inv_std,
+                                               sigma_out)
     check(load().sw_ars_update_multi_f64(ctypes.byref(p), S, n_dir, ptr(returns), ptr(deltas), ptr(policy),
                                          float(alpha), float(b), int(top_b), ptr(moments), n_rows, ptr(running),
                                          int(n_new_states), ptr(mean), ptr(inv_std), ptr(sigma_out), stream_ptr()),
           "sw_ars_update_multi_f64")
     return policy
-
-
-def _multi_shapes(p, policy, deltas, mean, inv_std):
-    """(S, N, device) of a multi-agent launch's policy [S, m, d] and deltas [S, N, m, d], checked with mean / inv_std."""
-    if policy.dim() != 3 or policy.shape[0] < 1:
-        raise _lib.SwimmerHipError(f"policy: expected float64 tensor of shape (S, m, d), got {tuple(policy.shape)}")
-    S = policy.shape[0]
-    _want(policy, "policy", (S, p.m, p.d))
-    if deltas.dim() != 4 or deltas.shape[1] < 1:
-        raise _lib.SwimmerHipError(f"deltas: expected float64 tensor of shape (S, N, m, d), got {tuple(deltas.shape)}")
-    N = deltas.shape[1]
-    _want(deltas, "deltas", (S, N, p.m, p.d))
-    if (mean is None) != (inv_std is None):
-        raise _lib.SwimmerHipError("mean and inv_std must be given together")
-    if mean is not None:
-        _want(mean, "mean", (S, p.d))
-        _want(inv_std, "inv_std", (S, p.d))
-    return S, N, policy.device
 
 
 def ars_gate_multi(p_base: SwParams, H: int, policy, deltas, nu: float, sim, sim_thresh, mean=None, inv_std=None,
@@ -550,14 +533,12 @@ def ars_gate_multi(p_base: SwParams, H: int, policy, deltas, nu: float, sim, sim
     ([S, 2N]) and `status` (int32 [S, 2N]) receive the simulator returns and status codes, row a as ars_gate gives
     them for agent a.  A simulator that breaks the parameter rule: SW_STATUS_PARAM, nothing admitted."""
     require_gpu()
-    S, N, dev = _multi_shapes(p_base, policy, deltas, mean, inv_std)
-    _want(sim, "sim", (S, 3))
-    _want(sim_thresh, "sim_thresh", (S,))
-    returns = _f64((S, 2 * N), dev) if returns is None else _want(returns, "returns", (S, 2 * N))
-    if status is not None:
-        _want_i32(status, "status", (S, 2 * N), dev)
-    admit = (torch.empty((S, N), dtype=torch.int32, device=dev) if admit is None
-             else _want_i32(admit, "admit", (S, N), dev))
+    S, N, on = _multi_shapes(p_base, policy, deltas, mean, inv_std)
+    _tensor(sim, "sim", (S, 3), on)
+    _tensor(sim_thresh, "sim_thresh", (S,), on)
+    returns = _out(returns, "returns", (S, 2 * N), on)
+    _opt(status, "status", (S, 2 * N), on, _I32)
+    admit = _out(admit, "admit", (S, N), on, _I32)
     check(load().sw_ars_gate_multi_f64(ctypes.byref(p_base), S, N, H, ptr(policy), ptr(deltas), float(nu), ptr(mean),
                                        ptr(inv_std), ptr(sim), ptr(sim_thresh), ptr(admit), ptr(returns),
                                        ptr(status), stream_ptr()), "sw_ars_gate_multi_f64")
@@ -570,18 +551,13 @@ def ars_pack_admitted(p: SwParams, admit, deltas, status=None, count=None, order
     -> (count int32 [S], order int32 [S, N]: the admitted indices ascending, then -1, packed [S, N, m, d]: their
     deltas in that order in entries 0..count-1; the entries behind them are not written)."""
     require_gpu()
-    if admit.dim() != 2 or admit.shape[0] < 1 or admit.shape[1] < 1:
-        raise _lib.SwimmerHipError(f"admit: expected int32 tensor of shape (S, N), got {tuple(admit.shape)}")
-    S, N = admit.shape
-    dev = deltas.device
-    _want_i32(admit, "admit", (S, N), dev)
-    _want(deltas, "deltas", (S, N, p.m, p.d))
-    if status is not None:
-        _want_i32(status, "status", (S, 2 * N), dev)
-    count = torch.empty(S, dtype=torch.int32, device=dev) if count is None else _want_i32(count, "count", (S,), dev)
-    order = (torch.empty((S, N), dtype=torch.int32, device=dev) if order is None
-             else _want_i32(order, "order", (S, N), dev))
-    packed = torch.zeros_like(deltas) if packed is None else _want(packed, "packed", (S, N, p.m, p.d))
+    on = _gpu(admit, "admit", 2)
+    S, N = _tensor(admit, "admit", (_Min(1), _Min(1)), on, _I32).shape
+    _tensor(deltas, "deltas", (S, N, p.m, p.d), on)
+    _opt(status, "status", (S, 2 * N), on, _I32)
+    count = _out(count, "count", (S,), on, _I32)
+    order = _out(order, "order", (S, N), on, _I32)
+    packed = _out(packed, "packed", (S, N, p.m, p.d), on, fill=0.0)
     check(load().sw_ars_pack_admitted_f64(ctypes.byref(p), S, N, ptr(admit), ptr(status), ptr(deltas), ptr(count),
                                           ptr(order), ptr(packed), stream_ptr()), "sw_ars_pack_admitted_f64")
     return count, order, packed
@@ -594,16 +570,12 @@ def ars_rollouts_multi_counted(p: SwParams, H: int, policy, deltas, nu: float, c
     entries 0..2 count[a] - 1 and its first moments_blocks(2 count[a]) moment rows; everything behind is left as it
     was (a new `returns` starts as NaN).  N = deltas.shape[1] is the maximum and sets the strides."""
     require_gpu()
-    S, N, dev = _multi_shapes(p, policy, deltas, mean, inv_std)
-    _want_i32(count, "count", (S,), dev)
+    S, N, on = _multi_shapes(p, policy, deltas, mean, inv_std)
+    _tensor(count, "count", (S,), on, _I32)
     if moments is not None:
-        _want(moments, "moments", (S, moments_blocks(2 * N), 2 * p.d))
-    if status is not None:
-        _want_i32(status, "status", (S, 2 * N), dev)
-    if returns is None:
-        returns = torch.full((S, 2 * N), float("nan"), dtype=torch.float64, device=dev)
-    else:
-        _want(returns, "returns", (S, 2 * N))
+        _tensor(moments, "moments", (S, moments_blocks(2 * N), 2 * p.d), on)
+    _opt(status, "status", (S, 2 * N), on, _I32)
+    returns = _out(returns, "returns", (S, 2 * N), on, fill=float("nan"))
     check(load().sw_ars_rollouts_multi_counted_f64(ctypes.byref(p), S, N, ptr(count), H, ptr(policy), ptr(deltas),
                                                    float(nu), ptr(mean), ptr(inv_std), ptr(returns), ptr(moments),
                                                    ptr(status), stream_ptr()), "sw_ars_rollouts_multi_counted_f64")
@@ -616,25 +588,9 @@ def ars_update_multi_counted(p: SwParams, H: int, count, returns, deltas, policy
     2 count[a] H (sw_ars_update_multi_counted_f64), in place; an agent with count 0 is left untouched.  Shapes as
     ars_update_multi with N the maximum; moments [S, rows >= moments_blocks(2N), 2d]."""
     require_gpu()
-    if returns.dim() != 2 or returns.shape[0] < 1 or returns.shape[1] < 2 or returns.shape[1] % 2:
-        raise _lib.SwimmerHipError(f"returns: expected float64 tensor of shape (S, 2N), got {tuple(returns.shape)}")
-    S, n_dir = returns.shape[0], returns.shape[1] // 2
-    _want(returns, "returns", (S, 2 * n_dir))
-    _want(policy, "policy", (S, p.m, p.d))
-    _want(deltas, "deltas", (S, n_dir, p.m, p.d))
-    _want_i32(count, "count", (S,), policy.device)
-    n_rows = 0
-    if running is not None:
-        _want(running, "running", (S, 1 + 2 * p.d))
-        _want(mean, "mean", (S, p.d))
-        _want(inv_std, "inv_std", (S, p.d))
-        if moments is None or moments.dim() != 3 or moments.shape[1] < moments_blocks(2 * n_dir):
-            raise _lib.SwimmerHipError("moments: expected float64 tensor of shape (S, rows >= moments_blocks(2N), 2d) "
-                                       "next to running")
-        n_rows = moments.shape[1]
-        _want(moments, "moments", (S, n_rows, 2 * p.d))
-    if sigma_out is not None:
-        _want(sigma_out, "sigma_out", (S,))
+    S, n_dir, n_rows, on = _multi_update_shapes(p, returns, deltas, policy, moments, True, running, mean, inv_std,
+                                                sigma_out)
+    _tensor(count, "count", (S,), on, _I32)
     check(load().sw_ars_update_multi_counted_f64(ctypes.byref(p), S, n_dir, ptr(count), H, ptr(returns), ptr(deltas),
                                                  ptr(policy), float(alpha), float(b), int(top_b), ptr(moments), n_rows,
                                                  ptr(running), ptr(mean), ptr(inv_std), ptr(sigma_out), stream_ptr()),
@@ -653,19 +609,16 @@ def safe_ars_rollouts_multi(p_real: SwParams, H: int, policy, deltas, nu: float,
     the step was refused), cost_max [A, 2N], first_refused / violations / status int32 [A, 2N].  A gated agent whose
     simulator breaks the parameter rule: SW_STATUS_PARAM, NaN returns, first_refused 0."""
     require_gpu()
-    A, N, dev = _multi_shapes(p_real, policy, deltas, None, None)
-    _want_i32(gated, "gated", (A,), dev)
-    _want(sim, "sim", (A, 3))
-    _want(sim_thresh, "sim_thresh", (A,))
-    _want(real_thresh, "real_thresh", (A,))
-    if cost_trace is not None:
-        _want(cost_trace, "cost_trace", (H, A, 2 * N))
-    if cost_max is not None:
-        _want(cost_max, "cost_max", (A, 2 * N))
+    A, N, on = _multi_shapes(p_real, policy, deltas, None, None)
+    _tensor(gated, "gated", (A,), on, _I32)
+    _tensor(sim, "sim", (A, 3), on)
+    _tensor(sim_thresh, "sim_thresh", (A,), on)
+    _tensor(real_thresh, "real_thresh", (A,), on)
+    _opt(cost_trace, "cost_trace", (H, A, 2 * N), on)
+    _opt(cost_max, "cost_max", (A, 2 * N), on)
     for name, t in (("first_refused", first_refused), ("violations", violations), ("status", status)):
-        if t is not None:
-            _want_i32(t, name, (A, 2 * N), dev)
-    returns = _f64((A, 2 * N), dev) if returns is None else _want(returns, "returns", (A, 2 * N))
+        _opt(t, name, (A, 2 * N), on, _I32)
+    returns = _out(returns, "returns", (A, 2 * N), on)
     check(load().sw_safe_ars_rollouts_multi_f64(ctypes.byref(p_real), A, N, H, ptr(policy), ptr(deltas), float(nu),
                                                 ptr(gated), ptr(sim), ptr(sim_thresh), ptr(real_thresh),
                                                 int(cost_kind), int(cost_index), ptr(returns), ptr(cost_trace),
@@ -689,19 +642,15 @@ def cacla_run(p: SwParams, n_iter: int, train: bool, gamma, alpha, noise, weight
     updated in place (weights only when training), actor_updates / status int32 [A] accumulated when given.
     Returns `rewards` [A, n_iter]."""
     require_gpu()
-    if gamma.dim() != 1 or gamma.shape[0] < 1:
-        raise _lib.SwimmerHipError(f"gamma: expected float64 tensor of shape (A,), got {tuple(gamma.shape)}")
-    A, dev = gamma.shape[0], gamma.device
-    _want(gamma, "gamma", (A,))
-    _want(alpha, "alpha", (A,))
-    _want(noise, "noise", (A, n_iter, p.m))
-    _want(weights, "weights", (A, p.n, cacla_net_doubles(p.n)))
-    _want(state, "state", (A, p.d))
-    if actor_updates is not None:
-        _want_i32(actor_updates, "actor_updates", (A,), dev)
-    if status is not None:
-        _want_i32(status, "status", (A,), dev)
-    rewards = _f64((A, n_iter), dev) if rewards is None else _want(rewards, "rewards", (A, n_iter))
+    on = _gpu(gamma, "gamma", 1)
+    A = _tensor(gamma, "gamma", (_Min(1),), on).shape[0]
+    _tensor(alpha, "alpha", (A,), on)
+    _tensor(noise, "noise", (A, n_iter, p.m), on)
+    _tensor(weights, "weights", (A, p.n, cacla_net_doubles(p.n)), on)
+    _tensor(state, "state", (A, p.d), on)
+    _opt(actor_updates, "actor_updates", (A,), on, _I32)
+    _opt(status, "status", (A,), on, _I32)
+    rewards = _out(rewards, "rewards", (A, n_iter), on)
     check(load().sw_cacla_run_f64(ctypes.byref(p), A, int(n_iter), 1 if train else 0, ptr(gamma), ptr(alpha),
                                   ptr(noise), ptr(weights), ptr(state), ptr(rewards), ptr(actor_updates),
                                   ptr(status), stream_ptr()), "sw_cacla_run_f64")
@@ -714,16 +663,9 @@ def ars_update_gathered(p: SwParams, n_dir: int, gathered, world: int, chunk: in
     """The ARS update reading the all-gathered result segments in place: `gathered` holds
     `world` segments [2*chunk returns | rows_chunk moment rows of 2d] (sw_ars_update_gathered_f64)."""
     require_gpu()
-    seg = 2 * chunk + rows_chunk * 2 * p.d
-    _want(gathered, "gathered", (world * seg,))
-    _want(policy, "policy", (p.m, p.d))
-    _want(deltas, "deltas", (deltas.shape[0], p.m, p.d))
-    if deltas.shape[0] < n_dir:
-        raise _lib.SwimmerHipError("deltas: fewer directions than n_dir")
-    if running is not None:
-        _want(running, "running", (1 + 2 * p.d,))
-        _want(mean, "mean", (p.d,))
-        _want(inv_std, "inv_std", (p.d,))
+    on = _gpu(gathered, "gathered", 1)
+    _tensor(gathered, "gathered", (world * (2 * chunk + rows_chunk * 2 * p.d),), on)
+    _update_shapes(p, on, n_dir, deltas, policy, running, mean, inv_std, sigma_out)
     check(load().sw_ars_update_gathered_f64(
         ctypes.byref(p), int(n_dir), ptr(gathered), int(world), int(chunk), int(rows_chunk),
         ptr(deltas), ptr(policy), float(alpha), float(b), int(top_b), ptr(running),
@@ -787,7 +729,7 @@ def cov_acc_doubles(p: SwParams, n_roll: int, H: int) -> int:
     followed by the pass's scratch (include/swimmer_hip.h)."""
     n = int(load().sw_cov_acc_doubles(ctypes.byref(p), int(n_roll), int(H)))
     if n < 0:
-        raise _lib.SwimmerHipError("sw_cov_acc_doubles: bad arguments")
+        raise SwimmerHipError("sw_cov_acc_doubles: bad arguments")
     return n
 
 
@@ -800,12 +742,9 @@ def traj_moments(p: SwParams, traj, acc=None):
     acc = new_cov_acc(p, n_roll, H, device) (sums + scratch), reusable for further passes of
     the same shape.  Deterministic (no floating-point atomics)."""
     require_gpu()
-    H, d, n_roll = traj.shape
-    _want(traj, "traj", (H, p.d, n_roll))
-    if acc is None:
-        acc = new_cov_acc(p, n_roll, H, traj.device)
-    if acc.dtype != torch.float64 or acc.dim() != 1 or acc.numel() < cov_acc_doubles(p, n_roll, H):
-        raise _lib.SwimmerHipError("acc: need a float64 vector of cov_acc_doubles(p, n_roll, H)")
+    on = _gpu(traj, "traj", 3)
+    H, _, n_roll = _tensor(traj, "traj", (_ANY, p.d, _ANY), on).shape
+    acc = _out(acc, "acc", (_Min(cov_acc_doubles(p, n_roll, H)),), on, fill=0.0)
     check(load().sw_traj_moments_f64(ctypes.byref(p), n_roll, H, ptr(traj), ptr(acc),
                                      stream_ptr()), "sw_traj_moments_f64")
     return acc
@@ -814,7 +753,9 @@ def traj_moments(p: SwParams, traj, acc=None):
 class ArsPipeline(object):
     """Handle of a native sw_ars_pipeline (include/swimmer_hip.h): the ring-buffered
     copy stream + progress flag + ride-along covariance schedule of one ARS iteration,
-    enqueued from C."""
+    enqueued from C.  rollouts() and update() are the training loop's per-iteration calls and the path bench.py's
+    aux_host_cost times: their device tensors are the agent's own buffers, allocated once, and go to the library
+    unchecked -- the one exception to this module's argument check."""
 
     def __init__(self):
         require_gpu()
@@ -858,7 +799,7 @@ class ArsPipeline(object):
                  nu, mean, inv_std, returns, traj, moments, cov_acc, status):
         """deltas_host: pinned CPU tensor [n_dir_total, m, d]; everything else on the GPU."""
         if not deltas_host.is_pinned() or not deltas_host.is_contiguous():
-            raise _lib.SwimmerHipError("deltas_host must be a contiguous pinned CPU tensor")
+            raise SwimmerHipError("deltas_host must be a contiguous pinned CPU tensor")
         check(load().sw_ars_iteration_rollouts_f64(
             self._h, slot, ctypes.byref(p), n_dir_total, dir_begin, n_dir, H,
             ctypes.c_void_p(deltas_host.data_ptr()), ptr(deltas_dev), ptr(policy), float(nu),
@@ -900,23 +841,19 @@ def lqr_cacla_run(ns: int, na: int, n_iter: int, safe: bool, threshold: int, cos
     are updated in place; the records rec_state [n_iter, ns, A], rec_action [n_iter, na, A], rec_reward [n_iter, A]
     and rec_admitted uint8 [n_iter, A] are written when given."""
     require_gpu()
-    if params.dim() != 2 or params.shape[1] < 1:
-        raise _lib.SwimmerHipError(f"params: expected float64 tensor of shape (P, A), got {tuple(params.shape)}")
-    A, dev = params.shape[1], params.device
-    _want(params, "params", (lqr_param_doubles(ns, na), A))
-    _want(noise, "noise", (n_iter, na, A))
-    _want(F, "F", (na, ns, A))
-    _want(V, "V", (ns, A))
-    _want(state, "state", (ns, A))
-    _want(last, "last", (ns + na + 1, A))
-    _want_i32(counters, "counters", (3, A), dev)
-    _want_i32(status, "status", (A,), dev)
-    for t, name, shape in ((rec_state, "rec_state", (n_iter, ns, A)), (rec_action, "rec_action", (n_iter, na, A)),
-                           (rec_reward, "rec_reward", (n_iter, A))):
-        if t is not None:
-            _want(t, name, shape)
-    if rec_admitted is not None and (rec_admitted.dtype != torch.uint8 or tuple(rec_admitted.shape) != (n_iter, A)):
-        raise _lib.SwimmerHipError(f"rec_admitted: expected uint8 tensor of shape {(n_iter, A)}")
+    on = _gpu(params, "params", 2)
+    A = _tensor(params, "params", (lqr_param_doubles(ns, na), _Min(1)), on).shape[1]
+    _tensor(noise, "noise", (n_iter, na, A), on)
+    _tensor(F, "F", (na, ns, A), on)
+    _tensor(V, "V", (ns, A), on)
+    _tensor(state, "state", (ns, A), on)
+    _tensor(last, "last", (ns + na + 1, A), on)
+    _tensor(counters, "counters", (3, A), on, _I32)
+    _tensor(status, "status", (A,), on, _I32)
+    _opt(rec_state, "rec_state", (n_iter, ns, A), on)
+    _opt(rec_action, "rec_action", (n_iter, na, A), on)
+    _opt(rec_reward, "rec_reward", (n_iter, A), on)
+    _opt(rec_admitted, "rec_admitted", (n_iter, A), on, torch.uint8)
     check(load().sw_lqr_cacla_run_f64(int(ns), int(na), A, int(n_iter), 1 if safe else 0, int(threshold), int(cost),
                                       ptr(params), ptr(noise), ptr(F), ptr(V), ptr(state), ptr(last), ptr(counters),
                                       ptr(status), ptr(rec_state), ptr(rec_action), ptr(rec_reward),
