@@ -45,6 +45,8 @@
  *                        safe_ars/experiment.py at once                safe_ars/ars.py:20-31, :111-153, :84-94
  *   sw_cacla_run_f64     CACLA_agent.run with TwoLayersNet / ActorFA / CriticFA, for every agent of the
  *                        hyper-parameter grid at once   cacla/cacla_agent.py:19-58, :135-199, cacla/swimmer_experiment.py:21-57
+ *   sw_cacla_safe_run_f64  the same learner behind the simulator gate of the safe agents (the combination the
+ *                        reference does not have)   cacla/cacla_safe_agent.py:161-188, safe_ars/ars.py:111-122
  *   sw_lqr_cacla_run_f64 CACLA_LQR_agent.run and the safe agents' run loops on the LQR environments, one agent per
  *                        lane   cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py, envs/gym_lqr/lqr_env.py
  *
@@ -483,6 +485,48 @@ int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64
 int sw_cacla_run_f64(const sw_params *p, int64_t n_agent, int32_t n_iter, int32_t train,
                      const double *gamma, const double *alpha, const double *noise, double *weights,
                      double *state, double *rewards, int32_t *actor_updates, int32_t *status, void *stream);
+
+/* ---- CACLA on the swimmer with safe exploration: the learner above inside the run loop of the reference's safe
+ * agents (cacla/cacla_safe_agent.py:161-188, LQR-only there), every real step gated by a one-step look-ahead in the
+ * agent's simulator (safe_ars/ars.py:111-122) ----
+ * sw_cacla_safe_run_f64 runs n_iter steps for n_agent agents, one wave each, always training.  Step t of a gated agent:
+ *   FA_act = actors(state); action = FA_act + noise[t]   (the noise of step t is consumed whether or not it is taken)
+ *   sim_state = step(state, action) with the agent's simulator constants (n, h and direction are `real`'s)
+ *   admitted = cost(sim_state) <= sim_thresh[a]           (a NaN cost or threshold refuses)
+ *   admitted: new_state, reward = the real step; violations += cost(new_state) > real_thresh[a] (false for NaN);
+ *             temp_diff, the critic's update and -- when temp_diff > 0 -- the actors' as sw_cacla_run_f64 does them
+ *             (V(new_state) with the old weights, the old W2 in the gradient); state = new_state; last_reward = reward
+ *   refused:  no step, no update: state and weights unchanged
+ *   rewards[t] = last_reward: a refused step repeats the last admitted step's reward, as the reference's list does; NaN
+ *             until the first admission, where the reference appends nothing
+ * An agent with gated[a] == 0 computes no look-ahead and takes every step: its rewards, weights, state, actor-update
+ * count and status have the bits of sw_cacla_run_f64(train = 1); its violations are counted too.
+ *   real          : the real swimmer (Gym model)
+ *   gamma, alpha, noise, weights, state, rewards, status : as sw_cacla_run_f64
+ *   gated         : [n_agent]  0: no gate
+ *   sim           : [n_agent][3] (l_i, m_i, k) of each agent's simulator, read for gated agents only; the constants are
+ *                   derived in the kernel by the function the host uses
+ *   sim_thresh    : [n_agent], read for gated agents only;  real_thresh : [n_agent]
+ *   cost_kind, cost_index : SW_COST_* as sw_safe_rollouts_f64
+ *   last_reward   : in/out [n_agent]; set it to NaN before the first launch of a run
+ *   admitted_rec  : NULL or [n_agent][n_iter], 1 / 0 per step
+ *   counters      : in/out [n_agent][3], += admitted steps, violations, actor updates; zero them before a run
+ *   first_refused : in/out [n_agent]; set it to -1 before a run: the kernel writes t_begin + t at the first refused
+ *                   step t while it is still -1
+ * A gated agent whose simulator breaks the parameter rule (SW_ERR_PARAM's) gets SW_STATUS_PARAM and every step refused;
+ * the other agents are unaffected.  Everything an agent carries is in/out, so a run can be split into launches
+ * (t_begin = the steps already run) and the split changes no bit.
+ * Errors, before any HIP call: a NULL pointer other than admitted_rec / status SW_ERR_NULL; n_agent < 1, n_agent >
+ * 2^31 - 1, n_iter < 0, t_begin < 0, t_begin + n_iter > 2^31 - 1, an unknown cost_kind or a cost_index outside 0..d-1
+ * with SW_COST_ABS_OBS SW_ERR_SIZE; twin model SW_ERR_PARAM; n outside 2..8 SW_ERR_SEGMENTS.  n_iter = 0 writes
+ * nothing. */
+int sw_cacla_safe_run_f64(const sw_params *real, int64_t n_agent, int32_t n_iter, int64_t t_begin,
+                          const double *gamma, const double *alpha, const double *noise,
+                          const int32_t *gated, const double *sim, const double *sim_thresh,
+                          const double *real_thresh, int32_t cost_kind, int32_t cost_index,
+                          double *weights, double *state, double *last_reward, double *rewards,
+                          int32_t *admitted_rec, int32_t *counters, int32_t *first_refused,
+                          int32_t *status, void *stream);
 
 /* ---- CACLA on LQR, with and without safe exploration (cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py,
  * envs/gym_lqr/lqr_env.py): whole runs of many independent agents in ONE launch, one agent per lane ----

@@ -20,6 +20,7 @@ ERR_NAMES = {0: "SW_OK", 1: "SW_ERR_NULL", 2: "SW_ERR_SEGMENTS", 3: "SW_ERR_SIZE
 STATUS_SINGULAR = 1
 STATUS_NONFINITE = 2
 STATUS_RANGE = 4
+STATUS_PARAM = 8        # a parameter set read on the device (a candidate's, an agent's simulator) breaks the parameter rule
 FLAG_ROLLOUT_LANE = 1   # sw_params.flags: force the lane-per-rollout kernel
 FLAG_ROLLOUT_QUAD = 2   # force the segment-per-lane kernels (quad: n = 3, row: n = 4..8)
 FLAG_MODEL_TWIN = 4     # integrate the native RL-Glue model (SwimmerEnvironment.cpp)
@@ -136,6 +137,8 @@ _PROTOTYPES = {
                                        + [ctypes.c_void_p] * 7),
     "sw_cacla_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
                          + [ctypes.c_void_p] * 9),
+    "sw_cacla_safe_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]
+                              + [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 9),
     "sw_lqr_cacla_run_f64": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 4
                              + [ctypes.c_void_p] * 13),
     "sw_traj_moments_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,

@@ -1,0 +1,187 @@
+"""CACLA on the swimmer with safe exploration: the learner of cacla_agent.CACLA_agent inside the run loop of the
+reference's safe agents (cacla/cacla_safe_agent.py:161-188, which the reference has for LQR only), every real step
+gated by a one-step look-ahead in a simulator (safe_ars/ars.py:111-122) -- on the fused kernel behind
+sw_cacla_safe_run_f64 (one wave per agent, whole chunks of steps in one launch).
+
+The host side is CACLA_agent's: the initial weights from torch (actors first, then the critic), the exploration noise
+from NumPy's legacy multivariate_normal, chunk by chunk.  The noise of a step is drawn whether or not the gate lets
+the step through, so a plain and a safe agent started from the same seeds see the same weights and the same noise.
+
+Rewards follow the reference's append rule (:177-188): nothing is appended before the first admitted step, and a
+refused step repeats the last reward.  The kernel writes NaN where nothing is appended; trim_rewards() drops it.
+"""
+import numpy as np
+import torch
+
+from . import safe_kernels
+from .cacla_agent import Uploader, draw_networks
+from .._lib import STATUS_SINGULAR, SwimmerHipError, dev_f64
+from ..safe_ars.ars import NativeCost
+
+CHUNK = 2048   # steps per launch, and per draw of the noise: CACLA_agent.chunk
+
+
+def trim_rewards(rewards, admitted):
+    """The reference's reward list from a run's rewards [n_iter] and admitted mask: the entries from the first
+    admitted step on (before it the reference appends nothing); all of them absent when no step was admitted."""
+    admitted = np.asarray(admitted, dtype=bool)
+    hit = np.flatnonzero(admitted)
+    return list(np.asarray(rewards)[hit[0]:]) if hit.size else []
+
+
+def _native(cost):
+    if not isinstance(cost, NativeCost) or cost.kind is None:
+        raise TypeError("cost must be a safe_ars.NativeCost (AbsObs(i) / MaxAbsThetaDot()): the gate is evaluated "
+                        f"in the kernel, not {type(cost).__name__}")
+    return cost
+
+
+def _same_model(env, sim_env):
+    if (sim_env.n != env.n or sim_env.h != env.h
+            or not np.array_equal(np.asarray(sim_env.direction, dtype=np.float64),
+                                  np.asarray(env.direction, dtype=np.float64))):
+        raise ValueError("sim_env must have the n, h and direction of env")
+
+
+class _SafeRun(object):
+    """The device side of a run of A agents behind the gate: what cacla_agent._Run holds, plus the gate's inputs and
+    the refusal bookkeeping.  draw(c) returns the next c steps' noise [A, c, m] on the host."""
+
+    def __init__(self, p, device, gammas, alphas, weights, state, gated, sims, sim_thresholds, real_thresholds, cost):
+        self.p, self.device, self.cost = p, torch.device(device), cost
+        A = self.A = len(gammas)
+        f64 = lambda v: dev_f64(np.asarray(v, dtype=np.float64), self.device)   # noqa: E731
+        self.gamma, self.alpha = f64(gammas), f64(alphas)
+        self.weights, self.state = dev_f64(weights, self.device), dev_f64(state, self.device)
+        self.gated = torch.as_tensor(np.asarray(gated, dtype=np.int32), device=self.device)
+        self.sim = f64(np.asarray(sims, dtype=np.float64).reshape(A, 3))
+        self.sim_thresh, self.real_thresh = f64(sim_thresholds), f64(real_thresholds)
+        self.last_reward = torch.full((A,), float("nan"), dtype=torch.float64, device=self.device)
+        self.counters = torch.zeros((A, 3), dtype=torch.int32, device=self.device)
+        self.first_refused = torch.full((A,), -1, dtype=torch.int32, device=self.device)
+        self.status = torch.zeros(A, dtype=torch.int32, device=self.device)
+
+    def run(self, n_iter, chunk, draw):
+        """-> (rewards [A, n_iter], NaN before an agent's first admission; admitted bool [A, n_iter])."""
+        m = self.p.m
+        if n_iter < 0 or chunk < 1:
+            raise SwimmerHipError("n_iter must be >= 0 and chunk >= 1")
+        if n_iter == 0:
+            return np.empty((self.A, 0)), np.empty((self.A, 0), dtype=bool)
+        sizes = [min(chunk, n_iter - t) for t in range(0, n_iter, chunk)]
+        rewards, admitted, t = [], [], 0
+        with torch.cuda.device(self.device):
+            up = Uploader(self.A * max(sizes) * m, self.device)
+            for c in sizes:
+                noise = up.upload(np.asarray(draw(c), dtype=np.float64).reshape(self.A, c, m))
+                rec = torch.empty((self.A, c), dtype=torch.int32, device=self.device)
+                rewards.append(safe_kernels.cacla_safe_run(
+                    self.p, c, t, self.gamma, self.alpha, noise, self.gated, self.sim, self.sim_thresh,
+                    self.real_thresh, self.cost.kind, self.cost.index, self.weights, self.state, self.last_reward,
+                    self.counters, self.first_refused, admitted_rec=rec, status=self.status))
+                admitted.append(rec)
+                t += c
+            return torch.cat(rewards, dim=1).cpu().numpy(), torch.cat(admitted, dim=1).cpu().numpy().astype(bool)
+
+
+class CACLA_SE_agent:
+    """CACLA_agent behind a simulator gate; `env` and `sim_env` are swimmer_amd.SwimmerEnv objects with the same n, h
+    and direction, `cost` a safe_ars.NativeCost.
+
+    After run(): actor_weights [n - 1, net_doubles(n)], critic_weights [net_doubles(n)], initial_weights, admitted
+    (steps taken), violations (steps taken whose cost exceeded real_threshold), actor_updates (steps with
+    temp_diff > 0), first_refused (the first refused step, None if none), admitted_steps (bool [n_iter]) and status
+    (SW_STATUS_* bits OR-ed over the run); the environment's state is the run's last."""
+
+    chunk = CHUNK
+
+    def __init__(self, gamma, alpha, sigma, sim_env, cost, real_threshold, sim_threshold):
+        self.gamma, self.alpha, self.sigma = gamma, alpha, sigma
+        self.sim_env = sim_env
+        self.cost = _native(cost)
+        self.real_threshold, self.sim_threshold = real_threshold, sim_threshold
+        self.actor_weights = self.critic_weights = self.initial_weights = self.admitted_steps = None
+        self.admitted = self.violations = self.actor_updates = self.status = 0
+        self.first_refused = None
+
+    def run(self, env, n_iter, H=1000):
+        n, m = env.n, env.n - 1
+        _same_model(env, self.sim_env)
+        assert env.observation_space.shape[0] == 2 * n + 2 and env.action_space.shape[0] == m
+        weights = draw_networks(n)                                   # torch's global generator
+        self.initial_weights = weights.copy()
+        state = np.asarray(env.reset(), dtype=np.float64)
+        cov = self.sigma * np.identity(m)
+        sim = [self.sim_env.l_i, self.sim_env.m_i, self.sim_env.k]
+        run = _SafeRun(env._params(), env.device, [self.gamma], [self.alpha], weights[None], state[None], [1], [sim],
+                       [self.sim_threshold], [self.real_threshold], self.cost)
+        rewards, admitted = run.run(int(n_iter), self.chunk,
+                                    lambda c: np.random.multivariate_normal(np.zeros(m), cov, size=c)[None])
+        rewards, self.admitted_steps = rewards[0], admitted[0]
+        w = run.weights.cpu().numpy()[0]
+        self.actor_weights, self.critic_weights = w[:m].copy(), w[m].copy()
+        self.status = int(run.status.cpu()[0])
+        self.admitted, self.violations, self.actor_updates = (int(v) for v in run.counters.cpu().numpy()[0])
+        first = int(run.first_refused.cpu()[0])
+        self.first_refused = None if first < 0 else first
+        if self.status & STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")           # numpy.linalg.solve's, inside env.step
+        env.set_state(run.state.cpu().numpy()[0].tolist())           # the environment has taken `admitted` steps
+        for i in range(H, n_iter, H):
+            if self.admitted_steps[:i + 1].any():                    # :190: only once there is a reward
+                print(f"Iteration {i}/{n_iter}: reward: {rewards[i]}")
+        return trim_rewards(rewards, self.admitted_steps)
+
+
+class CACLA_SE_Batch(object):
+    """A independent agents on one SwimmerEnv's model, gated or not, ONE launch per chunk of steps for all of them.
+
+    Agent a has (gammas[a], alphas[a], sigmas[a]), the simulator sims[a] = (l_i, m_i, k) with the thresholds
+    sim_thresholds[a] / real_thresholds[a], and draws its initial weights from torch.Generator().manual_seed(seeds[a])
+    and its noise from np.random.RandomState(seeds[a]): row a is, bit for bit, the single
+    agent after torch.manual_seed(seeds[a]); np.random.seed(seeds[a]) -- CACLA_SE_agent where gated[a] (default: all),
+    CACLA_agent where not (its simulator and simulator threshold are not read; its violations are still counted).
+    The global generators are not touched.
+
+    run() returns (rewards [A, n_iter], NaN before an agent's first admission, and admitted bool [A, n_iter]).
+    After it: weights [A, n, net_doubles(n)], state [A, d], status, admitted, violations, actor_updates and
+    first_refused (-1: none) [A]."""
+
+    def __init__(self, env, gammas, alphas, sigmas, seeds, sims, sim_thresholds, real_thresholds, cost, gated=None):
+        self.env, self.cost = env, _native(cost)
+        self.seeds = [int(s) for s in seeds]
+        A = self.n_agent = len(self.seeds)
+        vec = lambda v: np.asarray(v, dtype=np.float64).reshape(-1)   # noqa: E731
+        self.gammas, self.alphas, self.sigmas = vec(gammas), vec(alphas), vec(sigmas)
+        self.sim_thresholds, self.real_thresholds = vec(sim_thresholds), vec(real_thresholds)
+        self.sims = np.asarray(sims, dtype=np.float64).reshape(-1, 3)
+        self.gated = np.ones(A, dtype=np.int32) if gated is None else (np.asarray(gated).reshape(-1) != 0).astype(np.int32)
+        if A < 1 or not all(len(v) == A for v in (self.gammas, self.alphas, self.sigmas, self.sim_thresholds,
+                                                  self.real_thresholds, self.sims, self.gated)):
+            raise ValueError("gammas, alphas, sigmas, seeds, sims, the thresholds and gated must have the same "
+                             "length, at least 1")
+        self.weights = self.state = self.status = self.admitted = self.violations = self.actor_updates = None
+        self.first_refused = None
+
+    def run(self, n_iter, chunk=2048):
+        env, A = self.env, self.n_agent
+        n, m = env.n, env.n - 1
+        weights = np.stack([draw_networks(n, torch.Generator().manual_seed(s)) for s in self.seeds])
+        streams = [np.random.RandomState(s) for s in self.seeds]
+        covs = [s * np.identity(m) for s in self.sigmas]
+        state = np.asarray(env.reset(), dtype=np.float64)
+        zeros = np.zeros(m)
+
+        def draw(c):
+            return np.stack([rs.multivariate_normal(zeros, cov, size=c) for rs, cov in zip(streams, covs)])
+
+        run = _SafeRun(env._params(), env.device, self.gammas, self.alphas, weights, np.tile(state, (A, 1)),
+                       self.gated, self.sims, self.sim_thresholds, self.real_thresholds, self.cost)
+        rewards, admitted = run.run(int(n_iter), int(chunk), draw)
+        self.weights = run.weights.cpu().numpy()
+        self.state = run.state.cpu().numpy()
+        self.status = run.status.cpu().numpy()
+        counters = run.counters.cpu().numpy()
+        self.admitted, self.violations, self.actor_updates = counters[:, 0], counters[:, 1], counters[:, 2]
+        self.first_refused = run.first_refused.cpu().numpy()
+        return rewards, admitted

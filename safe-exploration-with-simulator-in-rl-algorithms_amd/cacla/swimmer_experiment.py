@@ -73,6 +73,30 @@ def grid(env, gammas, alphas, sigmas, n_iter, n_seed=3, out_dir="results/cacla/"
     return curves
 
 
+def safe_compare(env, sim, gamma, alpha, sigma, seeds, cost, real_threshold, sim_threshold, n_iter, chunk=2048):
+    """Plain against safe exploration from the same seeds: per seed one ungated agent and one agent gated by the
+    simulator `sim` (a SwimmerEnv with env's n, h and direction), all in ONE CACLA_SE_Batch.  Both agents of a seed
+    start from the same weights and see the same noise, so they part only where the gate refuses a step.
+
+    Returns a dict: rewards_plain, rewards_safe [n_seed, n_iter] (safe: NaN before a seed's first admitted step, a
+    refused step repeats the last reward), violations_plain, violations_safe, admitted_plain, admitted_safe [n_seed]
+    and first_refused [n_seed] (the safe agents'; -1: nothing refused)."""
+    from .cacla_safe_swimmer import CACLA_SE_Batch, _same_model
+    _same_model(env, sim)
+    seeds = [int(s) for s in seeds]
+    S = len(seeds)
+    if S < 1:
+        raise ValueError("safe_compare needs at least one seed")
+    batch = CACLA_SE_Batch(env, [gamma] * 2 * S, [alpha] * 2 * S, [sigma] * 2 * S, seeds + seeds,
+                           [[sim.l_i, sim.m_i, sim.k]] * 2 * S, [sim_threshold] * 2 * S, [real_threshold] * 2 * S,
+                           cost, gated=[0] * S + [1] * S)
+    rewards, _ = batch.run(n_iter, chunk=chunk)
+    return dict(rewards_plain=rewards[:S], rewards_safe=rewards[S:],
+                violations_plain=batch.violations[:S].copy(), violations_safe=batch.violations[S:].copy(),
+                admitted_plain=batch.admitted[:S].copy(), admitted_safe=batch.admitted[S:].copy(),
+                first_refused=batch.first_refused[S:].copy())
+
+
 def experience(env, gamma, alpha, sigma, n_iter, H=1000, n_seed=3, out_dir="results/cacla/"):
     """One setting of the grid (swimmer_experiment.py:21-44): (t, mean, std) of its n_seed agents."""
     mean, std = grid(env, [gamma], [alpha], [sigma], n_iter, n_seed=n_seed, out_dir=out_dir, H=H)[(gamma, alpha, sigma)]

@@ -80,6 +80,12 @@
 //                              (a hidden unit per lane, two from n = 6), the physics redundantly in every lane, the
 //                              n + 1 network outputs of a step summed through LDS in a fixed order and handed out
 //                              with v_readlane; instruction-issue bound like the latency forms
+//   swimmer_cacla_safe.hip (a translation unit of its own)
+//   cacla_safe_kernel<N>       sw_cacla_safe_run_f64: the same learner behind a per-step simulator gate, per agent gated
+//                              or not: cacla_kernel's layout and arithmetic (an ungated agent has its bits), plus the
+//                              simulator's look-ahead step and the cost redundantly in every lane, the admit decision
+//                              taken from the first lane into a scalar register, the real step and the update behind
+//                              a uniform branch; reward entry and admit flag staged per lane, stored once per block
 //   swimmer_lqr.hip (a translation unit of its own)
 //   lqr_cacla_kernel<NS,NA,MODE>  sw_lqr_cacla_run_f64: CACLA on LQR problems (plain, safe with a per-step or a fixed
 //                              simulator threshold), ONE AGENT PER LANE: models, F, V and state in VGPRs, no LDS, no
