@@ -28,6 +28,10 @@
  *   sw_ars_update_multi_counted_f64
  *                        the safe iteration (ars_agent.py:137-184) for every agent of ars/safe_exploration.py's sweep
  *                        at once (one Ray actor per agent in the reference)   ars/safe_exploration.py
+ *   sw_ars_gate_ensemble_f64
+ *                        the simulator threshold the reference leaves open (`# TODO compute sim_threshold`): the gate
+ *                        in an ensemble of simulators, a direction admitted only where every one admits it
+ *                                                                   ars/ars_agent.py:64-72, :144-157
  *   sw_traj_moments_f64  np.mean / np.cov over the saved states     ars/ars_agent.py:180-182
  *   sw_env1_step         the same step for ONE swimmer handed over in host memory (the Gym
  *                        surface and the RL-Glue env_step, SwimmerEnvironment.cpp:53-68)
@@ -411,6 +415,42 @@ int sw_ars_update_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t
                                     double alpha, double b, int64_t top_b, const double *moments,
                                     int64_t n_moment_rows, double *running, double *mean, double *inv_std,
                                     double *sigma_out, void *stream);
+
+/* ---- the gate in an ENSEMBLE of simulators ----
+ * sw_ars_gate_ensemble_f64: sw_ars_gate_multi_f64 with n_sim simulators per agent, and the fold over them.  The
+ * reference leaves its simulator threshold open (`# TODO compute sim_threshold`, ars_agent.py:70): threshold +
+ * alpha(H) epsilon with Lipschitz constants nobody knows.  Here a direction has to pass in EVERY simulator of a set
+ * that stands for the uncertainty -- several estimates, or samples on the epsilon-sphere around one -- and the worst
+ * simulated return takes the place of alpha epsilon.
+ *   base       : n, h, dir_* and flags of every simulator (its own l_i, m_i, k are validated but not used)
+ *   policy, deltas, mean / inv_std : per AGENT, as sw_ars_gate_multi_f64; shared by the agent's members, read in place
+ *   sim        : [n_agent][n_sim][3] (l_i, m_i, k) of member e of agent a; constants derived in the kernel, host's bits
+ *   sim_thresh : [n_agent]
+ *   member_returns / member_status : [n_agent][n_sim][2 n_dir]   member_admit : [n_agent][n_sim][n_dir]
+ *                member (a, e) has, bit for bit, the returns, status and flags of sw_ars_gate_f64 (dir_begin = 0) in
+ *                simulator sim[a][e] against sim_thresh[a] in the same form: member_admit = !(r+ <= thr) &&
+ *                !(r- <= thr), equality refuses, a NaN return or threshold admits.  All three are required: the fold
+ *                reads them.
+ *   admit      : [n_agent][n_dir]    the AND over e of member_admit
+ *   worst      : [n_agent][2 n_dir]  the minimum over e of the members' return r, taken as w = (x < w) ? x : w from
+ *                +inf in ascending e: a NaN never replaces w, and where every member's return is NaN worst is +inf
+ *   status     : NULL or [n_agent][2 n_dir]  the bitwise OR over e of the members' status (SW_STATUS_* are bit flags)
+ * A member whose simulator breaks the parameter rule gets SW_STATUS_PARAM, NaN returns and admits nothing (as in
+ * sw_ars_gate_multi_f64), so its whole agent admits nothing; the other agents are unaffected.  Where both status
+ * entries of a direction are 0, admit == !(worst+ <= thr) && !(worst- <= thr): a return with status 0 is finite, a
+ * refusing member holds one <= thr, and the minimum then is too.  admit, worst and status have the layout
+ * sw_ars_pack_admitted_f64 reads.
+ * Two launches on `stream`: the member kernels on the grid (workgroups of one agent, n_agent * n_sim), form and grid
+ * chosen as sw_ars_gate_multi_f64 chooses them for n_agent * n_sim agents (SW_FLAG_ROLLOUT_* and the model flag
+ * honoured), then the fold, one thread per (agent, direction), plain loads and stores: no result depends on timing.
+ * Errors, before any HIP call: a NULL required pointer, or one of mean / inv_std without the other: SW_ERR_NULL;
+ * n_agent < 1, n_sim < 1, n_agent * n_sim > 65535, n_dir < 1, n_dir > 2^23, H < 0 or 2^32 threads and more:
+ * SW_ERR_SIZE; parameters as everywhere. */
+int sw_ars_gate_ensemble_f64(const sw_params *base, int64_t n_agent, int64_t n_sim, int64_t n_dir, int32_t H,
+                             const double *policy, const double *deltas, double nu, const double *mean,
+                             const double *inv_std, const double *sim, const double *sim_thresh, int32_t *admit,
+                             double *worst, int32_t *status, double *member_returns, int32_t *member_status,
+                             int32_t *member_admit, void *stream);
 
 /* ---- safe_ars/experiment.py: Basic_ARS and Safe_ARS agents in lock-step, the per-step gate inside the rollout ----
  * sw_safe_ars_rollouts_multi_f64: the 2 n_dir exploration rollouts of n_agent agents in one launch, every rollout with

@@ -130,6 +130,10 @@ _PROTOTYPES = {
                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
                                                        ctypes.c_double, ctypes.c_int64, ctypes.c_void_p,
                                                        ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    # the gate in an ensemble of simulators: member launch and fold
+    "sw_ars_gate_ensemble_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
+                                 + [ctypes.c_void_p] * 11),
     # safe_ars/experiment.py: Basic_ARS / Safe_ARS rollouts of a batch of agents, the per-step gate in the kernel
     "sw_safe_ars_rollouts_multi_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]

@@ -35,6 +35,14 @@ errors the reference only meets later are raised at construction: sim_thresh=Non
 data_path raise ValueError; the gate is not sharded, so more than one rank raises
 NotImplementedError.
 
+The gate in an ENSEMBLE of simulators (sim_ensemble: a list of EnvParam, ars/ensemble.py): where the reference
+leaves `# TODO compute sim_threshold` (ars_agent.py:70), the gate of an iteration is one sw_ars_gate_ensemble_f64
+call -- every member's 2N rollouts, then the fold -- and a direction is admitted only where every member admits it.
+sim_thresh may then be None: the simulator threshold is agent_param.threshold itself, the worst member standing where
+alpha(H) * epsilon stood (a Threshold still adds its margin).  estimated_param is member 0; last_worst holds the worst
+simulated returns [2N] of the last iteration, read in the same copy as the flags.  The rest of the iteration is the
+safe iteration as it was.
+
 Streams: every launch goes to torch's CURRENT stream.  With a NCCL process group alive, work on
 the null (default) stream is implicitly ordered against the group's streams, which costs an
 iteration ~13 us of device-side waits (measured); run distributed training under a stream of
@@ -50,6 +58,8 @@ from .. import kernels
 from .._lib import (SwParams, SwimmerHipError, kernel_flags, numpy_global_uniform_pm1,
                     require_gpu)
 from .database import Database
+from .ensemble import check_ensemble, sim_rows
+from .ensemble_kernels import ars_gate_ensemble
 from .environment import Environment
 from . import sharding as _sh
 from .sharding import (all_gather_segments, returns_from_segments, segment_len,
@@ -102,11 +112,18 @@ class ARSAgent(object):
     def __init__(self, real_env_param, agent_param, data_path=None, seed=None,
                  guess_param=None, approx_error=None, sim_thresh=None, *, device=None,
                  process_group=None, record_trajectories=False, full_covariance=True,
-                 top_b=0, rollout_kernel="auto", direct_rccl=None, estimator_options=None):
+                 top_b=0, rollout_kernel="auto", direct_rccl=None, estimator_options=None, sim_ensemble=None):
         self.safe = bool(agent_param.safe)
+        if sim_ensemble is not None:
+            # the gate in an ensemble of simulators (ars/ensemble.py): the members ARE the estimation
+            if not self.safe:
+                raise ValueError("sim_ensemble gates a safe agent: agent_param.safe must be True")
+            if guess_param is not None or approx_error is not None:
+                raise ValueError("sim_ensemble is the estimation: guess_param and approx_error must be None")
+            sim_ensemble = check_ensemble(sim_ensemble, real_env_param)
         if self.safe:
             # the reference reaches `...` (ars_agent.py:64-65) / np.load(None) and fails later
-            if sim_thresh is None:
+            if sim_thresh is None and sim_ensemble is None:
                 raise ValueError("safe=True needs sim_thresh (a Threshold) to set the simulator threshold")
             if data_path is None:
                 raise ValueError("safe=True needs data_path: the real-world trajectories the agent loads")
@@ -141,9 +158,14 @@ class ARSAgent(object):
         self.violations = 0                            # real returns below threshold so far
         self.last_admitted = np.zeros(0, dtype=np.int64)
         self.estimated_param = self.sim_threshold = self.p_sim = None
+        self.sim_ensemble = sim_ensemble
+        self.last_worst = np.zeros(0)                  # the ensemble gate's worst simulated returns, [2N]
         if self.safe:
             self.database.load(data_path)
-            if guess_param is not None:
+            if sim_ensemble is not None:
+                print(f"Using an ensemble of {len(sim_ensemble)} simulators...")
+                self.estimated_param = sim_ensemble[0]
+            elif guess_param is not None:
                 from .estimator import Estimator    # CMA-ES: `cma` when it imports, else the built-in search
                 print("Using computed estimation...")
                 self.estimated_param = Estimator(self.database, guess_param,
@@ -155,7 +177,10 @@ class ARSAgent(object):
                 print("Using exact estimation...")
                 self.estimated_param = real_env_param
             print(f"Used estimation: {self.estimated_param}")
-            self.sim_threshold = simulator_threshold(agent_param, real_env_param, sim_thresh)
+            # with an ensemble the worst member stands where alpha * epsilon stood: the safety threshold itself,
+            # unless the caller still wants a margin on top
+            self.sim_threshold = (agent_param.threshold if sim_thresh is None else
+                                  simulator_threshold(agent_param, real_env_param, sim_thresh))
             print(f"Simulator threshold is {self.sim_threshold}")
             est = self.estimated_param
             self.p_sim = SwParams.make(est.n, est.l_i, est.m_i, est.k, est.h, (1.0, 0.0),
@@ -229,6 +254,18 @@ class ARSAgent(object):
             self._gate_returns = torch.empty(2 * N, **f64)
             # [admit (N) | simulator status (2N)]: read back with ONE device->host copy
             self._gate_flags = torch.zeros(3 * N, dtype=torch.int32, device=self.device)
+            if sim_ensemble is not None:
+                E = len(sim_ensemble)
+                # [worst (2N doubles) | admit (N) | folded status (2N)] in ONE buffer: still one device->host copy
+                self._gate_read = torch.zeros(16 * N + 12 * N, dtype=torch.uint8, device=self.device)
+                self._gate_worst = self._gate_read[:16 * N].view(torch.float64).view(1, 2 * N)
+                self._gate_flags = self._gate_read[16 * N:].view(torch.int32)
+                self._ens_sim = torch.as_tensor(sim_rows(sim_ensemble)[None], device=self.device)
+                self._ens_thresh = torch.full((1,), float(self.sim_threshold), **f64)
+                self._ens_thresh_host = self.sim_threshold
+                self._ens_returns = torch.empty((1, E, 2 * N), **f64)
+                self._ens_status = torch.zeros((1, E, 2 * N), dtype=torch.int32, device=self.device)
+                self._ens_admit = torch.zeros((1, E, N), dtype=torch.int32, device=self.device)
 
         # The exchange: torch.distributed (default), or -- direct_rccl=True / SWIMMER_DIRECT_RCCL=1 --
         # ncclAllGather called from native code on the critical stream with a communicator of this
@@ -433,10 +470,25 @@ class ARSAgent(object):
         else:
             host[...] = deltas
         self._gate_deltas.copy_(self._deltas_host[i], non_blocking=True)
-        kernels.ars_gate(self.p_sim, H, self._policy, self._gate_deltas, ap.nu, 0, N, self.sim_threshold,
-                         self._mean, self._inv_std, returns=self._gate_returns,
-                         status=self._gate_flags[N:], admit=self._gate_flags[:N])
-        flags = self._gate_flags.cpu().numpy()               # the one added device->host read
+        if self.sim_ensemble is not None:
+            # every member's gate and the fold over them: one call, and worst comes back with the flags
+            if self._ens_thresh_host != self.sim_threshold:      # sim_threshold is a public attribute: follow it
+                self._ens_thresh_host = self.sim_threshold
+                self._ens_thresh.fill_(float(self.sim_threshold))
+            ars_gate_ensemble(self.p_sim, H, self._policy[None], self._gate_deltas[None], ap.nu, self._ens_sim,
+                              self._ens_thresh, None if self._mean is None else self._mean[None],
+                              None if self._inv_std is None else self._inv_std[None],
+                              admit=self._gate_flags[:N].view(1, N), worst=self._gate_worst,
+                              status=self._gate_flags[N:].view(1, 2 * N), member_returns=self._ens_returns,
+                              member_status=self._ens_status, member_admit=self._ens_admit)
+            read = self._gate_read.cpu().numpy()             # the one added device->host read
+            self.last_worst = read[:16 * N].view(np.float64).copy()
+            flags = read[16 * N:].view(np.int32)
+        else:
+            kernels.ars_gate(self.p_sim, H, self._policy, self._gate_deltas, ap.nu, 0, N, self.sim_threshold,
+                             self._mean, self._inv_std, returns=self._gate_returns,
+                             status=self._gate_flags[N:], admit=self._gate_flags[:N])
+            flags = self._gate_flags.cpu().numpy()           # the one added device->host read
         if np.any(flags[N:] != 0):
             # a failed simulator rollout returns NaN, and NaN would admit its direction unnoticed
             raise np.linalg.LinAlgError("Singular matrix / non-finite state in a simulator rollout of the gate")

@@ -20,6 +20,12 @@ for bit, what ARSAgent(safe=True, seed=seeds[a], full_covariance=False) with the
 partial-admission rule included (ars_agent.py's docstring: the k admitted directions packed in ascending order,
 sigma_R over their 2k returns, the step divided by b, top_b clamped to k, nothing happens when k = 0).
 
+With sim_ensembles ([S][E] EnvParams, the same E for every agent; sim_params is then None) every agent gates in an
+ENSEMBLE of simulators (ars/ensemble.py): the first launch becomes sw_ars_gate_ensemble_f64 -- the members' gates and
+the fold, two launches behind one call -- whose admit flags and folded status have the layout the pack reads, so the
+other three launches are untouched and the host still reads nothing.  The worst simulated returns join the history.
+Row a is then ARSAgent(safe=True, seed=seeds[a], sim_ensemble=sim_ensembles[a], full_covariance=False), bit for bit.
+
 Differences from ARSAgent: a real return below the safety threshold is counted in `violations` but not printed (a
 sweep holds hundreds of agents); the estimation is the caller's (sim_params: see ars_agent.approximate_env_params); no
 trajectory store, no full covariance; one rank.
@@ -31,21 +37,38 @@ import torch.distributed as dist
 from .. import kernels
 from .._lib import SwParams, kernel_flags, require_gpu
 from .agent_batch import READ_EVERY, SeedStreams
+from .ensemble import check_ensemble, sim_rows
+from .ensemble_kernels import ars_gate_ensemble
 
 
 class SafeARSAgentBatch(object):
 
     def __init__(self, real_env_param, agent_param, seeds, sim_params, sim_thresholds, *, thresholds=None,
-                 device=None, top_b=0, rollout_kernel="auto"):
+                 device=None, top_b=0, rollout_kernel="auto", sim_ensembles=None):
         seeds = list(seeds)
         if not seeds:
             raise ValueError("SafeARSAgentBatch needs at least one seed")
         if not agent_param.safe:
             raise ValueError("SafeARSAgentBatch trains safe agents: agent_param.safe must be True "
                              "(ARSAgentBatch trains the unsafe ones)")
+        S = len(seeds)
+        if sim_ensembles is not None:
+            if sim_params is not None:
+                raise ValueError("SafeARSAgentBatch: sim_params (one simulator per agent) or sim_ensembles (several), "
+                                 "not both")
+            sim_ensembles = [list(ens) for ens in sim_ensembles]
+            if len(sim_ensembles) != S:
+                raise ValueError(f"SafeARSAgentBatch: {S} seeds need {S} sim_ensembles, got {len(sim_ensembles)}")
+            for a, ens in enumerate(sim_ensembles):
+                check_ensemble(ens, real_env_param, f"sim_ensembles[{a}]")
+                if len(ens) != len(sim_ensembles[0]):
+                    raise ValueError(f"sim_ensembles[{a}] holds {len(ens)} simulators, sim_ensembles[0] "
+                                     f"{len(sim_ensembles[0])}: the agents of a batch share the ensemble size")
+            sim_params = [ens[0] for ens in sim_ensembles]      # what ARSAgent calls estimated_param
+        elif sim_params is None:
+            raise ValueError("SafeARSAgentBatch needs sim_params or sim_ensembles")
         sim_params = list(sim_params)
         sim_thresholds = [float(t) for t in sim_thresholds]
-        S = len(seeds)
         if len(sim_params) != S or len(sim_thresholds) != S:
             raise ValueError(f"SafeARSAgentBatch: {S} seeds need {S} sim_params and {S} sim_thresholds, got "
                              f"{len(sim_params)} and {len(sim_thresholds)}")
@@ -76,6 +99,7 @@ class SafeARSAgentBatch(object):
         self.seeds, self.S = seeds, S
         self.real_env_param, self.agent_param = real_env_param, agent_param
         self.sim_params, self.sim_thresholds = sim_params, np.array(sim_thresholds)
+        self.sim_ensembles = sim_ensembles
         self.thresholds = np.array(thresholds)
         self.top_b = int(top_b)
         self.safe = True
@@ -109,6 +133,15 @@ class SafeARSAgentBatch(object):
         self._order_hist = torch.zeros((READ_EVERY, S, N), **i32)
         self._gate_returns = torch.zeros((S, 2 * N), **f64)
         self._admit = torch.zeros((S, N), **i32)
+        self.last_worst = [np.zeros(0) for _ in range(S)]
+        self.min_admitted_worst = np.full(S, np.inf)        # over every admitted direction of every iteration read
+        if sim_ensembles is not None:
+            E = len(sim_ensembles[0])
+            self._ens_sim = torch.as_tensor(np.stack([sim_rows(ens) for ens in sim_ensembles]), device=self.device)
+            self._worst_hist = torch.zeros((READ_EVERY, S, 2 * N), **f64)
+            self._ens_returns = torch.zeros((S, E, 2 * N), **f64)
+            self._ens_status = torch.zeros((S, E, 2 * N), **i32)
+            self._ens_admit = torch.zeros((S, E, N), **i32)
         # deltas: drawn on the host into a small ring of pinned buffers, ONE host-to-device copy per iteration
         self._streams = SeedStreams(seeds)
         self._deltas = torch.empty((S, N, self.m, self.d), **f64)
@@ -164,9 +197,15 @@ class SafeARSAgentBatch(object):
         self._copied[k].record()
         gate_status, count = self._gate_status_hist[row], self._count_hist[row]
         returns = self._ret_hist[row]
-        kernels.ars_gate_multi(self.params, ap.H, self._policy, self._deltas, ap.nu, self._sim, self._sim_thresh,
-                               self._mean, self._inv_std, returns=self._gate_returns, status=gate_status,
-                               admit=self._admit)
+        if self.sim_ensembles is not None:
+            ars_gate_ensemble(self.params, ap.H, self._policy, self._deltas, ap.nu, self._ens_sim, self._sim_thresh,
+                              self._mean, self._inv_std, admit=self._admit, worst=self._worst_hist[row],
+                              status=gate_status, member_returns=self._ens_returns, member_status=self._ens_status,
+                              member_admit=self._ens_admit)
+        else:
+            kernels.ars_gate_multi(self.params, ap.H, self._policy, self._deltas, ap.nu, self._sim, self._sim_thresh,
+                                   self._mean, self._inv_std, returns=self._gate_returns, status=gate_status,
+                                   admit=self._admit)
         kernels.ars_pack_admitted(self.params, self._admit, self._deltas, status=gate_status, count=count,
                                   order=self._order_hist[row], packed=self._packed)
         kernels.ars_rollouts_multi_counted(self.params, ap.H, self._policy, self._packed, ap.nu, count, self._mean,
@@ -187,6 +226,7 @@ class SafeARSAgentBatch(object):
         gate_status = self._gate_status_hist.index_select(0, idx).cpu().numpy()
         counts = self._count_hist.index_select(0, idx).cpu().numpy()
         order = self._order_hist.index_select(0, idx).cpu().numpy()
+        worst = (self._worst_hist.index_select(0, idx).cpu().numpy() if self.sim_ensembles is not None else None)
         out, bad = [], set()
         for i in range(len(rows)):
             per_agent = []
@@ -196,11 +236,16 @@ class SafeARSAgentBatch(object):
                 if gate_status[i, s].any() or status[i, s, :2 * k].any():
                     bad.add(s)
                 self.violations[s] += int(np.count_nonzero(r < self.thresholds[s]))
+                if worst is not None and k > 0:
+                    w = worst[i, s].reshape(-1, 2)[order[i, s, :k]]
+                    self.min_admitted_worst[s] = min(self.min_admitted_worst[s], float(w.min()))
                 per_agent.append(r)
             out.append(per_agent)
         last = len(rows) - 1
         self.last_admitted = [order[last, s, :int(counts[last, s])].astype(np.int64) for s in range(self.S)]
         self.last_returns = out[last]
+        if worst is not None:
+            self.last_worst = [worst[last, s].copy() for s in range(self.S)]
         if bad:
             raise np.linalg.LinAlgError("Singular matrix / non-finite state in a simulator or real rollout of "
                                         + ", ".join(f"agent {s} (seed {self.seeds[s]})" for s in sorted(bad)))

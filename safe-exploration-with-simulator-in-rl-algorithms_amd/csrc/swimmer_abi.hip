@@ -131,6 +131,41 @@ MultiPlan plan_multi(const sw_params *p, Member FormLaunchers::*op, int64_t n_ag
     return m;
 }
 
+// The fold behind the member launch of sw_ars_gate_ensemble_f64: one thread per (agent, direction) walks the agent's
+// n_sim members in ascending order -- admit = AND of the members' flags, worst = their smallest return by
+// `w = (x < w) ? x : w` from +inf (a NaN never replaces w), status = OR of theirs.  Plain loads and stores, no atomics
+// and no hand-over between workgroups: the result does not depend on timing.  A kernel of its own, not a tail of the
+// member kernels, for the reason ars_pack_admitted_kernel is one: the last workgroup to finish would have to be found
+// with a device-scope counter, and the member kernels would no longer be the gate kernels' bodies.
+constexpr int kFoldBlock = 256;
+__global__ void __launch_bounds__(kFoldBlock)
+ars_gate_fold_kernel(int64_t n_pair, int64_t n_dir, int32_t n_sim, const double *__restrict__ member_returns,
+                     const int32_t *__restrict__ member_status, const int32_t *__restrict__ member_admit,
+                     int32_t *__restrict__ admit, double *__restrict__ worst, int32_t *__restrict__ status)
+{
+    const int64_t i = (int64_t)blockIdx.x * kFoldBlock + threadIdx.x;   // agent * n_dir + direction
+    if (i >= n_pair) return;
+    const int64_t agent = i / n_dir, dir = i - agent * n_dir;
+    double w0 = __builtin_inf(), w1 = __builtin_inf();
+    int32_t s0 = 0, s1 = 0, all_admit = 1;
+    for (int32_t e = 0; e < n_sim; ++e) {
+        const int64_t member = agent * n_sim + e;
+        const double x0 = member_returns[(member * n_dir + dir) * 2], x1 = member_returns[(member * n_dir + dir) * 2 + 1];
+        w0 = (x0 < w0) ? x0 : w0;
+        w1 = (x1 < w1) ? x1 : w1;
+        s0 |= member_status[(member * n_dir + dir) * 2];
+        s1 |= member_status[(member * n_dir + dir) * 2 + 1];
+        all_admit &= member_admit[member * n_dir + dir] != 0 ? 1 : 0;
+    }
+    admit[i] = all_admit;
+    worst[2 * i] = w0;
+    worst[2 * i + 1] = w1;
+    if (status) {
+        status[2 * i] = s0;
+        status[2 * i + 1] = s1;
+    }
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -285,6 +320,36 @@ int sw_ars_gate_multi_f64(const sw_params *base, int64_t n_agent, int64_t n_dir,
     const SafeMultiArgs a{policy, deltas, mean, inv_std, returns, /*moments=*/nullptr, status, sim, sim_thresh, admit,
                           /*count=*/nullptr};
     return launchers(m.plan.form).gate_multi(base, m.plan, n_agent, 2 * n_dir, H, a, nu, (hipStream_t)stream);
+}
+
+// The gate in an ensemble of simulators: the member launch (the form and the grid of sw_ars_gate_multi_f64 for
+// n_agent * n_sim agents), then the fold.  Both on `stream`, nothing in between.
+int sw_ars_gate_ensemble_f64(const sw_params *base, int64_t n_agent, int64_t n_sim, int64_t n_dir, int32_t H,
+                             const double *policy, const double *deltas, double nu, const double *mean,
+                             const double *inv_std, const double *sim, const double *sim_thresh, int32_t *admit,
+                             double *worst, int32_t *status, double *member_returns, int32_t *member_status,
+                             int32_t *member_admit, void *stream)
+{
+    int rc = check_params(base);
+    if (rc) return rc;
+    if (n_agent < 1 || n_sim < 1 || n_agent > 65535 || n_sim > 65535) return SW_ERR_SIZE;   // the product cannot overflow
+    const int64_t n_member = n_agent * n_sim;
+    const MultiPlan m = plan_multi(base, &FormLaunchers::gate_ensemble, n_member, n_dir, H);
+    if (!m.fits) return SW_ERR_SIZE;
+    if (!policy || !deltas || !sim || !sim_thresh || !admit || !worst || !member_returns || !member_status ||
+        !member_admit)
+        return SW_ERR_NULL;
+    if ((mean == nullptr) != (inv_std == nullptr)) return SW_ERR_NULL;
+    const EnsembleArgs a{policy, deltas, mean, inv_std, member_returns, member_status, sim, sim_thresh, member_admit,
+                         (int32_t)n_sim};
+    rc = launchers(m.plan.form).gate_ensemble(base, m.plan, n_member, 2 * n_dir, H, a, nu, (hipStream_t)stream);
+    if (rc) return rc;
+    // fewer threads than the member launch has (one per direction against two rollouts per direction and member)
+    const int64_t n_pair = n_agent * n_dir;
+    hipLaunchKernelGGL(ars_gate_fold_kernel, dim3((unsigned)((n_pair + kFoldBlock - 1) / kFoldBlock)), dim3(kFoldBlock),
+                       0, (hipStream_t)stream, n_pair, n_dir, (int32_t)n_sim, member_returns, member_status,
+                       member_admit, admit, worst, status);
+    return launch_status();
 }
 
 int sw_ars_rollouts_multi_counted_f64(const sw_params *p, int64_t n_agent, int64_t n_dir, const int32_t *count,

@@ -58,6 +58,11 @@
 //                              agents.  The gate form takes every agent's simulator constants and threshold from device
 //                              arrays (the view derives C with sw::consts_of), the counted form every agent's number
 //                              of rollouts; both are the form's body behind swimmer_rollout_multi.inc
+//   ars_gate_ens_{oct3,quad3,row,lane}_kernel  (in the form's file)
+//                              the member launch of sw_ars_gate_ensemble_f64: the gate body behind the same view with
+//                              SW_MULTI_ENSEMBLE 1, grid (workgroups of one agent, n_agent * n_sim): member (a, e) runs
+//                              agent a's policy and deltas in simulator sim[a][e] and writes its own slices;
+//                              ars_gate_fold_kernel (swimmer_abi.hip) then folds the members into admit / worst / status
 //   swimmer_rollout_safe_multi.hip
 //   safe_ars_multi_oct3_kernel<COST,VIOL>, safe_ars_multi_lane_kernel<N>
 //                              sw_safe_ars_rollouts_multi_f64: the ARS exploration rollouts of MANY AGENTS with the
@@ -228,6 +233,20 @@ constexpr int row_counted_loop_pad(int n, bool mom)
     return n == 4 ? (mom ? 14 : 0) : n == 5 ? (mom ? 8 : 12) : n == 6 ? (mom ? 8 : 10) : n == 7 ? (mom ? 10 : 14)
                                                                                              : (mom ? 6 : 1);
 }
+#endif
+
+// The member kernels of the ensemble gate (ars_gate_ens_*_kernel, sw_ars_gate_ensemble_f64) run the gate body behind
+// the ensemble view, whose prologue divides blockIdx.y by the ensemble size: pads of their own once more.  NOT swept
+// either: each puts the hot loop at the offset of the form's ars_gate_multi_*_kernel (scripts/multi_loop_offsets.py
+// prints these pairs too).  -DSW_ENS_LOOP_PAD=k overrides all of them.
+#ifdef SW_ENS_LOOP_PAD
+constexpr int oct_gate_ens_loop_pad() { return SW_ENS_LOOP_PAD; }
+constexpr int quad_gate_ens_loop_pad() { return SW_ENS_LOOP_PAD; }
+constexpr int row_gate_ens_loop_pad(int) { return SW_ENS_LOOP_PAD; }
+#else
+constexpr int oct_gate_ens_loop_pad() { return 2; }
+constexpr int quad_gate_ens_loop_pad() { return 0; }
+constexpr int row_gate_ens_loop_pad(int n) { return n == 4 ? 10 : n == 5 ? 4 : n == 6 ? 12 : n == 7 ? 12 : 7; }
 #endif
 
 // steps per trip of the quad kernel's loop (measurement knob; 2 measured +5 ns per step)
@@ -593,6 +612,22 @@ struct SafeMultiArgs {
 };
 using SafeMultiLauncher = int(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                               const SafeMultiArgs &a, double nu, hipStream_t stream);
+// The member launch of the ensemble gate (sw_ars_gate_ensemble_f64): every agent's gate in n_sim simulators, grid
+// (workgroups of one agent, n_agent * n_sim).  policy / deltas / mean / inv_std / sim_thresh are per AGENT as in
+// SafeMultiArgs; sim [n_agent][n_sim][3] and the outputs -- returns / status [n_agent][n_sim][2 n_dir], admit
+// [n_agent][n_sim][n_dir] -- are per MEMBER.  A struct of its own: SafeMultiArgs is a kernel argument of the
+// ars_gate_multi_* and ars_counted_* kernels as it is.
+struct EnsembleArgs {
+    const double *policy, *deltas, *mean, *inv_std;
+    double *returns;
+    int32_t *status;
+    const double *sim, *sim_thresh;
+    int32_t *admit;
+    int32_t n_sim;
+};
+// n_member = n_agent * n_sim: the grid's second dimension
+using EnsembleLauncher = int(const sw_params *p, const RolloutPlan &plan, int64_t n_member, int64_t n_roll, int32_t H,
+                             const EnsembleArgs &a, double nu, hipStream_t stream);
 // Safe exploration (sw_safe_rollouts_f64).
 using SafeLauncher = int(const sw_params *real, const sw_params *sim, const RolloutPlan &plan, int64_t n_roll,
                          int32_t H, const double *policies, int32_t cost_kind, int32_t cost_index, double sim_thresh,
@@ -621,6 +656,7 @@ struct FormLaunchers {
     SafeMultiLauncher *const gate_multi, *const counted;
     SafeLauncher *const safe;                     // (none in the quad form)
     SafeArsMultiLauncher *const safe_ars_multi;   // (mirror-quad and lane only; swimmer_rollout_safe_multi.hip)
+    EnsembleLauncher *const gate_ensemble;        // the member launch of sw_ars_gate_ensemble_f64
 };
 extern FormLaunchers kOct3Launchers, kQuad3Launchers, kRowLaunchers, kLaneLaunchers;
 

@@ -74,6 +74,22 @@ ars_gate_multi_lane_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch
 #include "swimmer_rollout_lane.inc"
 #undef SW_GATE_BODY
 }
+
+// The member launch of sw_ars_gate_ensemble_f64 in the lane form: the same body behind the view with
+// SW_MULTI_ENSEMBLE 1 (blockIdx.y = agent * n_sim + member).
+#define SW_MULTI_ENSEMBLE 1
+template <int N, bool TWIN>
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_ens_lane_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::EnsembleArgs all, double nu)
+{
+    constexpr bool ARS = true;
+#include "swimmer_rollout_multi.inc"
+    const sw::TwinConsts T{sim_l, sim_m, sim_k, base.h, base.dirx, base.diry};
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_lane.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_ENSEMBLE
 #undef SW_MULTI_GATE
 
 #define SW_MULTI_COUNTED 1
@@ -166,6 +182,16 @@ int launch_gate_multi_lane(const sw_params *p, const RolloutPlan &plan, int64_t 
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
+int launch_gate_ens_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_member, int64_t n_roll, int32_t H,
+                         const EnsembleArgs &a, double nu, hipStream_t stream)
+{
+    const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
+        launch_agent_grid(ars_gate_ens_lane_kernel<N.value, TWIN.value>, plan, n_member, n_roll, stream,
+                          make_consts(p), n_roll, H, a, nu);
+    }, is_twin(p));
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
 int launch_counted_lane(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                         const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
@@ -197,5 +223,6 @@ SafeArsMultiLauncher launch_safe_ars_multi_lane;   // swimmer_rollout_safe_multi
 
 namespace sw_launch __attribute__((visibility("hidden"))) {
 FormLaunchers kLaneLaunchers = {launch_lane,         launch_gate_lane, launch_multi_lane, launch_gate_multi_lane,
-                                launch_counted_lane, launch_safe_lane, launch_safe_ars_multi_lane};
+                                launch_counted_lane, launch_safe_lane, launch_safe_ars_multi_lane,
+                                launch_gate_ens_lane};
 }  // namespace sw_launch

@@ -195,6 +195,37 @@ ars_gate_multi_oct3_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch
 #undef SW_GATE_BODY
 }
 #undef SW_MULTI_PAD
+
+// The member launch of sw_ars_gate_ensemble_f64 in the two n = 3 forms: the same bodies behind the view with
+// SW_MULTI_ENSEMBLE 1 (blockIdx.y = agent * n_sim + member: the agent's policy and deltas, the member's simulator and
+// outputs).
+#define SW_MULTI_ENSEMBLE 1
+#define SW_MULTI_PAD quad_gate_ens_loop_pad()
+__global__ void __launch_bounds__(kRollBlock)
+ars_gate_ens_quad3_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::EnsembleArgs all, double nu,
+                          SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_quad3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+
+#define SW_MULTI_PAD oct_gate_ens_loop_pad()
+__global__ void __launch_bounds__(kOctBlock)
+ars_gate_ens_oct3_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::EnsembleArgs all, double nu,
+                         SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_oct3.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+#undef SW_MULTI_ENSEMBLE
 #undef SW_MULTI_GATE
 
 #define SW_MULTI_COUNTED 1
@@ -339,6 +370,22 @@ int launch_gate_multi_quad3(const sw_params *p, const RolloutPlan &plan, int64_t
     return launch_status();
 }
 
+int launch_gate_ens_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_member, int64_t n_roll, int32_t H,
+                         const EnsembleArgs &a, double nu, hipStream_t stream)
+{
+    launch_agent_grid(ars_gate_ens_oct3_kernel, plan, n_member, n_roll, stream, make_consts(p), n_roll, H, a, nu,
+                      kNoSide);
+    return launch_status();
+}
+
+int launch_gate_ens_quad3(const sw_params *p, const RolloutPlan &plan, int64_t n_member, int64_t n_roll, int32_t H,
+                          const EnsembleArgs &a, double nu, hipStream_t stream)
+{
+    launch_agent_grid(ars_gate_ens_quad3_kernel, plan, n_member, n_roll, stream, make_consts(p), n_roll, H, a, nu,
+                      kNoSide);
+    return launch_status();
+}
+
 int launch_counted_oct3(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                         const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
@@ -380,7 +427,9 @@ SafeArsMultiLauncher launch_safe_ars_multi_oct3;   // swimmer_rollout_safe_multi
 
 namespace sw_launch __attribute__((visibility("hidden"))) {
 FormLaunchers kOct3Launchers = {launch_oct3,         launch_gate_oct3, launch_multi_oct3, launch_gate_multi_oct3,
-                                launch_counted_oct3, launch_safe_oct3, launch_safe_ars_multi_oct3};
+                                launch_counted_oct3, launch_safe_oct3, launch_safe_ars_multi_oct3,
+                                launch_gate_ens_oct3};
 FormLaunchers kQuad3Launchers = {launch_quad3,         launch_gate_quad3, launch_multi_quad3, launch_gate_multi_quad3,
-                                 launch_counted_quad3, /*safe=*/nullptr,  /*safe_ars_multi=*/nullptr};
+                                 launch_counted_quad3, /*safe=*/nullptr,  /*safe_ars_multi=*/nullptr,
+                                 launch_gate_ens_quad3};
 }  // namespace sw_launch

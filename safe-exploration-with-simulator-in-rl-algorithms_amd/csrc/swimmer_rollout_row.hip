@@ -76,6 +76,24 @@ ars_gate_multi_row_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch:
 #undef SW_GATE_BODY
 }
 #undef SW_MULTI_PAD
+
+// The member launch of sw_ars_gate_ensemble_f64 in the row form: the same body behind the view with
+// SW_MULTI_ENSEMBLE 1 (blockIdx.y = agent * n_sim + member).
+#define SW_MULTI_ENSEMBLE 1
+#define SW_MULTI_PAD row_gate_ens_loop_pad(N)
+template <int N>
+__global__ void __launch_bounds__(kRowBlock, (N <= 6 ? 2 : 1))
+ars_gate_ens_row_kernel(sw::Consts base, int64_t n_roll, int32_t H, sw_launch::EnsembleArgs all, double nu,
+                        SideJob side)
+{
+    constexpr bool ARS = true, TRAJ = false, MOM = false;
+#include "swimmer_rollout_multi.inc"
+#define SW_GATE_BODY 1
+#include "swimmer_rollout_row.inc"
+#undef SW_GATE_BODY
+}
+#undef SW_MULTI_PAD
+#undef SW_MULTI_ENSEMBLE
 #undef SW_MULTI_GATE
 
 #define SW_MULTI_COUNTED 1
@@ -304,6 +322,16 @@ int launch_gate_multi_row(const sw_params *p, const RolloutPlan &plan, int64_t n
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
 
+int launch_gate_ens_row(const sw_params *p, const RolloutPlan &plan, int64_t n_member, int64_t n_roll, int32_t H,
+                        const EnsembleArgs &a, double nu, hipStream_t stream)
+{
+    const bool known_n = with_n<4, 8>(p->n, [&](auto N) {
+        launch_agent_grid(ars_gate_ens_row_kernel<N.value>, plan, n_member, n_roll, stream, make_consts(p), n_roll, H,
+                          a, nu, kNoSide);
+    });
+    return known_n ? launch_status() : SW_ERR_SEGMENTS;
+}
+
 int launch_counted_row(const sw_params *p, const RolloutPlan &plan, int64_t n_agent, int64_t n_roll, int32_t H,
                        const SafeMultiArgs &a, double nu, hipStream_t stream)
 {
@@ -333,5 +361,6 @@ int launch_safe_row(const sw_params *real, const sw_params *sim, const RolloutPl
 
 namespace sw_launch __attribute__((visibility("hidden"))) {
 FormLaunchers kRowLaunchers = {launch_row,         launch_gate_row, launch_multi_row,          launch_gate_multi_row,
-                               launch_counted_row, launch_safe_row, /*safe_ars_multi=*/nullptr};
+                               launch_counted_row, launch_safe_row, /*safe_ars_multi=*/nullptr,
+                               launch_gate_ens_row};
 }  // namespace sw_launch

@@ -35,6 +35,11 @@ PAIRS += [(f"ars_counted_quad3_kernelILb{mom}E", f"rollout_quad3_kernelILb1ELb0E
 PAIRS += [(f"ars_counted_row_kernelILi{n}ELb{mom}E", f"rollout_row_kernelILi{n}ELb1ELb0ELb{mom}E", 1)
           for n in range(4, 9) for mom in (1, 0)]
 
+# the ensemble gate's member kernels next to the form's multi-agent gate kernel (*_gate_ens_loop_pad)
+PAIRS += [("ars_gate_ens_oct3_kernel", "ars_gate_multi_oct3_kernel", 0),
+          ("ars_gate_ens_quad3_kernel", "ars_gate_multi_quad3_kernel", 0)]
+PAIRS += [(f"ars_gate_ens_row_kernelILi{n}E", f"ars_gate_multi_row_kernelILi{n}E", 1) for n in range(4, 9)]
+
 
 def kernel(lines, fragment):
     start = next(i for i, l in enumerate(lines) if fragment in l and l.endswith(">:"))
