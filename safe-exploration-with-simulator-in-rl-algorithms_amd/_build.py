@@ -12,8 +12,9 @@ LIB_PATH = os.environ.get("SWIMMER_HIP_LIB") or os.path.join(CSRC, "libswimmer_h
 OBJ_DIR = LIB_PATH + ".obj"    # a library's objects live next to it: A/B builds (SWIMMER_HIP_LIB) never mix theirs
 # the translation units: swimmer_kernels.hip includes the kernel families' files (FAMILIES; its header says why
 # they have to be compiled together), swimmer_abi.hip is the rollout entry points and the ARS pipeline,
-# swimmer_cacla.hip the CACLA learner (a unit of its own: nothing in it is shared with the families), swimmer_lqr.hip
-# CACLA on the LQR problems (likewise), swimmer_cacla_safe.hip the CACLA learner behind the simulator gate (likewise)
+# swimmer_cacla.hip CACLA on the swimmer (a unit of its own: nothing in it is shared with the families),
+# swimmer_cacla_safe.hip the same behind the simulator gate (likewise; the learner both run is swimmer_cacla_learner.h),
+# swimmer_lqr.hip CACLA on the LQR problems (a unit of its own as well)
 SOURCES = ["swimmer_kernels.hip", "swimmer_abi.hip", "swimmer_cacla.hip", "swimmer_lqr.hip", "swimmer_cacla_safe.hip",
            "direct_comm.cpp", "host_rng.cpp"]
 FAMILIES = ["swimmer_rollout_row.hip", "swimmer_rollout_n3.hip", "swimmer_rollout_lane.hip",
@@ -25,7 +26,7 @@ HEADERS = ["rlglue_env.cpp", os.path.join("..", "..", "include", "rlglue_swimmer
            "swimmer_rollout_quad3.inc", "swimmer_rollout_oct3.inc", "swimmer_rollout_octp3.inc",
            "swimmer_rollout_row.inc", "swimmer_rollout_multi.inc", "swimmer_rollout_safe_oct3.inc",
            "swimmer_rollout_safe_lane.inc", "swimmer_rollout_safe_multi.inc", "swimmer_update.inc", "swimmer_quad3.h",
-           "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h",
+           "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h", "swimmer_cacla_learner.h",
            os.path.join("..", "..", "include", "swimmer_hip.h")] + FAMILIES
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + os.environ.get("SWIMMER_HIPCC_EXTRA", "").split()
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC"]

@@ -88,10 +88,48 @@ class Uploader(object):
         return out
 
 
+def chunk_sizes(n_iter, chunk):
+    """The steps of each launch of a run of n_iter steps, at most `chunk` per launch."""
+    if n_iter < 0 or chunk < 1:
+        raise SwimmerHipError("n_iter must be >= 0 and chunk >= 1")
+    return [min(chunk, n_iter - t) for t in range(0, n_iter, chunk)]
+
+
+def run_chunks(device, A, m, sizes, draw, launch):
+    """The chunk loop of a run of A agents, plain or gated.  draw(c) returns the next c steps' noise [A, c, m] on the
+    host; launch(c, t, noise) starts the c steps from step t on with that noise on the device and returns the
+    chunk's per-step outputs, a tuple of [A, c] device tensors.  Chunk k + 1 is drawn while chunk k runs (launches
+    are asynchronous), and the outputs come back in one copy each at the end: a list of [A, sum(sizes)] arrays."""
+    outs, t = [], 0
+    with torch.cuda.device(device):
+        up = Uploader(A * max(sizes) * m, device)
+        for c in sizes:
+            outs.append(launch(c, t, up.upload(np.asarray(draw(c), dtype=np.float64).reshape(A, c, m))))
+            t += c
+        return [(col[0] if len(col) == 1 else torch.cat(col, dim=1)).cpu().numpy() for col in zip(*outs)]
+
+
+def draw_batch(env, seeds, sigmas):
+    """What fixes the random streams of a batch: agent a's initial weights from torch.Generator().manual_seed(seeds[a])
+    and its noise from np.random.RandomState(seeds[a]) with variance sigmas[a], as the single classes draw theirs
+    from the global generators after seeding both with seeds[a].  -> (weights [A, n, net_doubles(n)], draw, the reset
+    state once per agent [A, d]); draw(c) is the next c steps' noise [A, c, m]."""
+    n, m = env.n, env.n - 1
+    weights = np.stack([draw_networks(n, torch.Generator().manual_seed(s)) for s in seeds])
+    streams = [np.random.RandomState(s) for s in seeds]
+    covs = [s * np.identity(m) for s in sigmas]
+    state = np.asarray(env.reset(), dtype=np.float64)
+    zeros = np.zeros(m)
+
+    def draw(c):
+        return np.stack([rs.multivariate_normal(zeros, cov, size=c) for rs, cov in zip(streams, covs)])
+
+    return weights, draw, np.tile(state, (len(seeds), 1))
+
+
 class _Run(object):
-    """The device side of a run of A agents: weights, state, counters and the chunk loop.  draw(c) returns the next
-    c steps' noise [A, c, m] on the host; chunk k + 1 is drawn while chunk k runs (launches are asynchronous), and
-    the rewards come back in one copy at the end."""
+    """The device side of a run of A agents: weights, state and counters.  run() is run_chunks() over
+    kernels.cacla_run; draw(c) returns the next c steps' noise [A, c, m] on the host."""
 
     def __init__(self, p, device, gammas, alphas, weights, state):
         self.p, self.device = p, torch.device(device)
@@ -105,23 +143,18 @@ class _Run(object):
         self.actor_updates = torch.zeros(A, dtype=torch.int32, device=self.device)
 
     def run(self, n_iter, chunk, train, draw):
-        m = self.p.m
-        if n_iter < 0 or chunk < 1:
-            raise SwimmerHipError("n_iter must be >= 0 and chunk >= 1")
-        if n_iter == 0:
+        sizes = chunk_sizes(n_iter, chunk)
+        if not sizes:
             return np.empty((self.A, 0))
-        sizes = [min(chunk, n_iter - t) for t in range(0, n_iter, chunk)]
-        if not train and len(sizes) > 1:
+        if not train:
             # the actors keep seeing the observation the LAUNCH started from (include/swimmer_hip.h): one launch
             sizes = [n_iter]
-        out = []
-        with torch.cuda.device(self.device):
-            up = Uploader(self.A * max(sizes) * m, self.device)
-            for c in sizes:
-                noise = up.upload(np.asarray(draw(c), dtype=np.float64).reshape(self.A, c, m))
-                out.append(kernels.cacla_run(self.p, c, train, self.gamma, self.alpha, noise, self.weights,
-                                             self.state, actor_updates=self.actor_updates, status=self.status))
-            return (out[0] if len(out) == 1 else torch.cat(out, dim=1)).cpu().numpy()
+
+        def launch(c, t, noise):
+            return (kernels.cacla_run(self.p, c, train, self.gamma, self.alpha, noise, self.weights, self.state,
+                                      actor_updates=self.actor_updates, status=self.status),)
+
+        return run_chunks(self.device, self.A, self.p.m, sizes, draw, launch)[0]
 
 
 class CACLA_agent:
@@ -185,18 +218,9 @@ class CACLABatch(object):
         self.weights = self.state = self.status = self.actor_updates = None
 
     def run(self, n_iter, chunk=2048, train=True):
-        env, A = self.env, self.n_agent
-        n, m = env.n, env.n - 1
-        weights = np.stack([draw_networks(n, torch.Generator().manual_seed(s)) for s in self.seeds])
-        streams = [np.random.RandomState(s) for s in self.seeds]
-        covs = [s * np.identity(m) for s in self.sigmas]
-        state = np.asarray(env.reset(), dtype=np.float64)
-        zeros = np.zeros(m)
-
-        def draw(c):
-            return np.stack([rs.multivariate_normal(zeros, cov, size=c) for rs, cov in zip(streams, covs)])
-
-        run = _Run(env._params(), env.device, self.gammas, self.alphas, weights, np.tile(state, (A, 1)))
+        env = self.env
+        weights, draw, state = draw_batch(env, self.seeds, self.sigmas)
+        run = _Run(env._params(), env.device, self.gammas, self.alphas, weights, state)
         rewards = run.run(int(n_iter), int(chunk), bool(train), draw)
         self.weights = run.weights.cpu().numpy()
         self.state = run.state.cpu().numpy()

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import safe_kernels
-from .cacla_agent import Uploader, draw_networks
-from .._lib import STATUS_SINGULAR, SwimmerHipError, dev_f64
+from .cacla_agent import chunk_sizes, draw_batch, draw_networks, run_chunks
+from .._lib import STATUS_SINGULAR, dev_f64
 from ..safe_ars.ars import NativeCost
 
 CHUNK = 2048   # steps per launch, and per draw of the noise: CACLA_agent.chunk
@@ -63,25 +63,19 @@ class _SafeRun(object):
 
     def run(self, n_iter, chunk, draw):
         """-> (rewards [A, n_iter], NaN before an agent's first admission; admitted bool [A, n_iter])."""
-        m = self.p.m
-        if n_iter < 0 or chunk < 1:
-            raise SwimmerHipError("n_iter must be >= 0 and chunk >= 1")
-        if n_iter == 0:
+        sizes = chunk_sizes(n_iter, chunk)
+        if not sizes:
             return np.empty((self.A, 0)), np.empty((self.A, 0), dtype=bool)
-        sizes = [min(chunk, n_iter - t) for t in range(0, n_iter, chunk)]
-        rewards, admitted, t = [], [], 0
-        with torch.cuda.device(self.device):
-            up = Uploader(self.A * max(sizes) * m, self.device)
-            for c in sizes:
-                noise = up.upload(np.asarray(draw(c), dtype=np.float64).reshape(self.A, c, m))
-                rec = torch.empty((self.A, c), dtype=torch.int32, device=self.device)
-                rewards.append(safe_kernels.cacla_safe_run(
-                    self.p, c, t, self.gamma, self.alpha, noise, self.gated, self.sim, self.sim_thresh,
-                    self.real_thresh, self.cost.kind, self.cost.index, self.weights, self.state, self.last_reward,
-                    self.counters, self.first_refused, admitted_rec=rec, status=self.status))
-                admitted.append(rec)
-                t += c
-            return torch.cat(rewards, dim=1).cpu().numpy(), torch.cat(admitted, dim=1).cpu().numpy().astype(bool)
+
+        def launch(c, t, noise):
+            rec = torch.empty((self.A, c), dtype=torch.int32, device=self.device)
+            return safe_kernels.cacla_safe_run(
+                self.p, c, t, self.gamma, self.alpha, noise, self.gated, self.sim, self.sim_thresh, self.real_thresh,
+                self.cost.kind, self.cost.index, self.weights, self.state, self.last_reward, self.counters,
+                self.first_refused, admitted_rec=rec, status=self.status), rec
+
+        rewards, admitted = run_chunks(self.device, self.A, self.p.m, sizes, draw, launch)
+        return rewards, admitted.astype(bool)
 
 
 class CACLA_SE_agent:
@@ -164,19 +158,10 @@ class CACLA_SE_Batch(object):
         self.first_refused = None
 
     def run(self, n_iter, chunk=2048):
-        env, A = self.env, self.n_agent
-        n, m = env.n, env.n - 1
-        weights = np.stack([draw_networks(n, torch.Generator().manual_seed(s)) for s in self.seeds])
-        streams = [np.random.RandomState(s) for s in self.seeds]
-        covs = [s * np.identity(m) for s in self.sigmas]
-        state = np.asarray(env.reset(), dtype=np.float64)
-        zeros = np.zeros(m)
-
-        def draw(c):
-            return np.stack([rs.multivariate_normal(zeros, cov, size=c) for rs, cov in zip(streams, covs)])
-
-        run = _SafeRun(env._params(), env.device, self.gammas, self.alphas, weights, np.tile(state, (A, 1)),
-                       self.gated, self.sims, self.sim_thresholds, self.real_thresholds, self.cost)
+        env = self.env
+        weights, draw, state = draw_batch(env, self.seeds, self.sigmas)
+        run = _SafeRun(env._params(), env.device, self.gammas, self.alphas, weights, state, self.gated, self.sims,
+                       self.sim_thresholds, self.real_thresholds, self.cost)
         rewards, admitted = run.run(int(n_iter), int(chunk), draw)
         self.weights = run.weights.cpu().numpy()
         self.state = run.state.cpu().numpy()

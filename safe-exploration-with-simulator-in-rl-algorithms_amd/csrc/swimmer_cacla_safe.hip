@@ -1,15 +1,11 @@
-// swimmer_cacla_safe.hip -- CACLA on the swimmer WITH SAFE EXPLORATION: the learner of swimmer_cacla.hip
-// (cacla/cacla_agent.py:165-190) inside the run loop of the reference's safe agents (cacla/cacla_safe_agent.py:161-188),
-// every real step gated by a one-step look-ahead in the agent's simulator (safe_ars/ars.py:111-122).  Whole runs of
-// MANY INDEPENDENT AGENTS in one launch, one wave per agent.  A translation unit of its own: no existing code object
-// depends on it.
+// swimmer_cacla_safe.hip -- CACLA on the swimmer WITH SAFE EXPLORATION: the learner of swimmer_cacla_learner.h
+// (cacla/cacla_agent.py:165-190; its header explains layout and summation order) inside the run loop of the reference's
+// safe agents (cacla/cacla_safe_agent.py:161-188), every real step gated by a one-step look-ahead in the agent's
+// simulator (safe_ars/ars.py:111-122).  Whole runs of MANY INDEPENDENT AGENTS in one launch, one wave per agent.  A
+// translation unit of its own: no existing code object depends on it.
 //
-// The layout is cacla_kernel's (swimmer_cacla.hip, whose header explains it): the hidden units of an agent's n
-// networks in the lanes of its wave, a unit's weights in registers for the whole run, every lane integrating the same
-// swimmer, a network's output summed through LDS in the fixed order of sum_hidden() and handed out with v_readlane,
-// the noise loaded a 64-step block ahead.  The learner's arithmetic -- forward, temp_diff, the two SGD steps -- is
-// written expression by expression as it is there, so that an UNGATED agent (gated[a] == 0: no look-ahead, every step
-// taken) has the bits of sw_cacla_run_f64(train = 1).
+// An UNGATED agent (gated[a] == 0: no look-ahead, every step taken) runs the learner's pieces in cacla_kernel's order
+// and so has the bits of sw_cacla_run_f64(train = 1).
 //
 // One step of a gated agent: FA_act = actors(state), action = FA_act + noise[t] (consumed whether or not the step is
 // taken); the simulator's step from the same state with the same action (sw::euler_step with the agent's own
@@ -18,28 +14,11 @@
 // lane into a scalar register, and the real step with the learner's update behind it is a uniform branch.  A refused
 // step changes nothing.  Lane t & 63 keeps step t's reward entry (the last admitted step's reward, NaN before the
 // first admission) and its admit flag; both are stored once per 64-step block.
-#include "swimmer_launch.h"
+#include "swimmer_cacla_learner.h"
 
 namespace {
 
 constexpr int kSafeCaclaBlock = kWave;   // one wave per agent, one workgroup per wave
-constexpr int kHid = SW_CACLA_HIDDEN;
-
-// v of lane `src` (wave-uniform) in every lane, through scalar registers.
-__device__ __forceinline__ double lane_value(double v, int src)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
-
-// The order of a network's sum (swimmer_cacla.hip); __dadd_rn: no reassociation, no contraction.
-__device__ __forceinline__ double sum_hidden(const double *q)
-{
-    const double a0 = __dadd_rn(q[0], q[1]), a1 = __dadd_rn(q[2], q[3]), a2 = __dadd_rn(q[4], q[5]);
-    const double a3 = __dadd_rn(q[6], q[7]), a4 = __dadd_rn(q[8], q[9]), a5 = __dadd_rn(q[10], q[11]);
-    return __dadd_rn(__dadd_rn(__dadd_rn(a0, a1), __dadd_rn(a2, a3)), __dadd_rn(a4, a5));
-}
 
 struct SafeCaclaArgs {
     const double *gamma, *alpha, *noise;
@@ -54,37 +33,21 @@ __global__ void __launch_bounds__(kSafeCaclaBlock)
 cacla_safe_kernel(sw::Consts C, int32_t n_iter, int32_t t_begin, int32_t cost_kind, int32_t cost_index,
                   SafeCaclaArgs a)
 {
-    constexpr int D = 2 * N + 2, M = N - 1;
-    constexpr int UPL = (kHid * N <= kWave) ? 1 : 2;   // hidden units per lane
-    constexpr int LPN = kHid / UPL;                    // lanes per network
-    constexpr int NETD = SW_CACLA_NET_DOUBLES(N);
-    static_assert(LPN * N <= kWave && kHid % UPL == 0, "an agent's networks must fit one wave");
+    using S = cacla::Shape<N>;
+    constexpr int D = S::D, M = S::M, UPL = S::UPL;
     __shared__ double prod[2][kWave * UPL];            // products of the forward at s (0) and at s' (1)
 
     const int lane = threadIdx.x;
     const int64_t agent = blockIdx.x;
-    const bool valid = lane < LPN * N;
-    const int net = valid ? lane / LPN : N - 1;          // idle lanes shadow the critic's unit 0 and store nothing
-    const int j0 = valid ? (lane % LPN) * UPL : 0;
+    const cacla::Place pl = cacla::place_of<N>(lane);
 
-    double *const wn = a.weights + (agent * N + net) * NETD;
+    double *const wn = a.weights + (agent * N + pl.net) * S::NETD;
     double W1[UPL][D], b1[UPL], W2[UPL], b2;
-#pragma unroll
-    for (int u = 0; u < UPL; ++u) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) W1[u][i] = wn[(j0 + u) * D + i];
-        b1[u] = wn[kHid * D + j0 + u];
-        W2[u] = wn[kHid * D + kHid + j0 + u];
-    }
-    b2 = wn[kHid * D + 2 * kHid];
+    cacla::load_weights<N>(wn, pl.j0, W1, b1, W2, b2);
 
     double *const sp = a.state + agent * D;
-    double gdx = sp[0], gdy = sp[1], th[N], thd[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        th[i] = sp[2 + 2 * i];
-        thd[i] = sp[3 + 2 * i];
-    }
+    double gdx, gdy, th[N], thd[N];
+    cacla::load_state<N>(sp, gdx, gdy, th, thd);
     const double gam = a.gamma[agent], alp = a.alpha[agent];
 
     // the gate: whether there is one, and the agent's simulator and thresholds (all wave-uniform)
@@ -100,15 +63,9 @@ cacla_safe_kernel(sw::Consts C, int32_t n_iter, int32_t t_begin, int32_t cost_ki
         sim_thresh = uniform_f64(a.sim_thresh[agent]);
     }
 
-    // this lane's step of a 64-step block: its n - 1 noise values
     const double *const np = a.noise + agent * (int64_t)n_iter * M;
-    auto load_noise = [&](int32_t t0, double (&dst)[M]) {
-        const int64_t t = (int64_t)t0 + lane;
-#pragma unroll
-        for (int i = 0; i < M; ++i) dst[i] = (t < n_iter) ? np[t * M + i] : 0.0;
-    };
     double nz[M], nz_next[M];
-    load_noise(0, nz);
+    cacla::load_noise<N>(np, n_iter, 0, lane, nz);
 
     double *const rp = a.rewards + agent * (int64_t)n_iter;
     int32_t *const ap = a.admitted_rec ? a.admitted_rec + agent * (int64_t)n_iter : nullptr;
@@ -120,44 +77,16 @@ cacla_safe_kernel(sw::Consts C, int32_t n_iter, int32_t t_begin, int32_t cost_ki
     int32_t n_upd = 0, n_adm = 0, n_viol = 0, refused_at = -1;
 
     for (int32_t t0 = 0; t0 < n_iter; t0 += kWave) {
-        load_noise(t0 + kWave, nz_next);                 // a block ahead: consumed 64 steps from here
+        cacla::load_noise<N>(np, n_iter, t0 + kWave, lane, nz_next);   // a block ahead: consumed 64 steps from here
         const int32_t steps = (n_iter - t0 < kWave) ? n_iter - t0 : kWave;
         for (int32_t k = 0; k < steps; ++k) {
             thmax = sw::track_angle_range<N>(thmax, th);
-            double x[D];
-            x[0] = gdx;
-            x[1] = gdy;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                x[2 + 2 * i] = th[i];
-                x[3 + 2 * i] = thd[i];
-            }
-            // forward of every network at x.  relu as torch's: NaN passes (z <= 0 is false), and so does its gradient
-            double h[UPL];
+            double x[D], h[UPL], out[N], act[M];
             bool off[UPL];
+            cacla::observe<N>(gdx, gdy, th, thd, x);
+            cacla::forward<N>(prod[0], pl, W1, b1, W2, b2, x, h, off, out);
 #pragma unroll
-            for (int u = 0; u < UPL; ++u) {
-                double z0 = b1[u], z1 = W1[u][1] * x[1];
-                z0 = __builtin_fma(W1[u][0], x[0], z0);
-#pragma unroll
-                for (int i = 2; i < D; i += 2) {
-                    z0 = __builtin_fma(W1[u][i], x[i], z0);
-                    z1 = __builtin_fma(W1[u][i + 1], x[i + 1], z1);
-                }
-                const double z = z0 + z1;
-                off[u] = z <= 0.0;
-                h[u] = off[u] ? 0.0 : z;
-                prod[0][lane * UPL + u] = W2[u] * h[u];
-            }
-            __syncthreads();
-            const double own = __dadd_rn(sum_hidden(&prod[0][net * kHid]), b2);
-            double out[N];                               // actors' outputs, then V(x): wave-uniform
-#pragma unroll
-            for (int i = 0; i < N; ++i) out[i] = lane_value(own, i * LPN);
-
-            double act[M];                               // Gaussian policy: mean + noise
-#pragma unroll
-            for (int i = 0; i < M; ++i) act[i] = __dadd_rn(out[i], lane_value(nz[i], k));
+            for (int i = 0; i < M; ++i) act[i] = __dadd_rn(out[i], cacla::lane_value(nz[i], k));   // mean + noise
 
             bool admit = true;
             if (gated) {   // uniform: the simulator's look-ahead from the real state (cacla_safe_agent.py:166-168)
@@ -180,44 +109,8 @@ cacla_safe_kernel(sw::Consts C, int32_t n_iter, int32_t t_begin, int32_t cost_ki
                 n_adm += 1;
                 n_viol += (safe_cost<N>(cost_kind, cost_index, gdx, gdy, th, thd) > real_thresh) ? 1 : 0;
                 last = rew;
-                // V(s') with the weights from before this step's update (cacla_agent.py:186)
-#pragma unroll
-                for (int u = 0; u < UPL; ++u) {
-                    double z0 = b1[u], z1 = W1[u][1] * gdy;
-                    z0 = __builtin_fma(W1[u][0], gdx, z0);
-#pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        z0 = __builtin_fma(W1[u][2 + 2 * i], th[i], z0);
-                        z1 = __builtin_fma(W1[u][3 + 2 * i], thd[i], z1);
-                    }
-                    const double z = z0 + z1;
-                    prod[1][lane * UPL + u] = W2[u] * ((z <= 0.0) ? 0.0 : z);
-                }
-                __syncthreads();
-                const double v_new = lane_value(__dadd_rn(sum_hidden(&prod[1][net * kHid]), b2), (N - 1) * LPN);
-                const double td = __dadd_rn(__dadd_rn(rew, __dmul_rn(gam, v_new)), -out[N - 1]);
-                const bool better = td > 0.0;            // false for NaN: no actor update, as the reference
-                n_upd += better ? 1 : 0;
-                // this lane's network: the critic steps by alpha td, actor i by alpha (action_i - FA_act_i) if better
-                double st = __dmul_rn(alp, td);
-                bool upd = true;
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    const double sa = __dmul_rn(alp, __dadd_rn(act[i], -out[i]));
-                    st = (net == i) ? sa : st;
-                    upd = (net == i) ? better : upd;
-                }
-                if (upd) {
-#pragma unroll
-                    for (int u = 0; u < UPL; ++u) {
-                        const double sg = st * (off[u] ? 0.0 : W2[u]);   // the OLD W2
-                        W2[u] = __builtin_fma(st, h[u], W2[u]);
-#pragma unroll
-                        for (int i = 0; i < D; ++i) W1[u][i] = __builtin_fma(sg, x[i], W1[u][i]);
-                        b1[u] += sg;
-                    }
-                    b2 += st;
-                }
+                cacla::learn<N>(prod[1], pl, W1, b1, W2, b2, gdx, gdy, th, thd, x, h, off, out, act, rew, gam, alp,
+                                n_upd);
             } else {
                 refused_at = (refused_at < 0) ? t0 + k : refused_at;
             }
@@ -232,26 +125,9 @@ cacla_safe_kernel(sw::Consts C, int32_t n_iter, int32_t t_begin, int32_t cost_ki
         for (int i = 0; i < M; ++i) nz[i] = nz_next[i];
     }
 
-    if (valid) {
-#pragma unroll
-        for (int u = 0; u < UPL; ++u) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) wn[(j0 + u) * D + i] = W1[u][i];
-            wn[kHid * D + j0 + u] = b1[u];
-            wn[kHid * D + kHid + j0 + u] = W2[u];
-        }
-        if (j0 == 0) wn[kHid * D + 2 * kHid] = b2;
-    }
+    if (pl.valid) cacla::store_weights<N>(wn, pl.j0, W1, b1, W2, b2);
     if (lane == 0) {
-        sp[0] = gdx;
-        sp[1] = gdy;
-        bool fin = isfinite(gdx) && isfinite(gdy);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            sp[2 + 2 * i] = th[i];
-            sp[3 + 2 * i] = thd[i];
-            fin = fin && isfinite(th[i]) && isfinite(thd[i]);
-        }
+        const bool fin = cacla::store_state<N>(sp, gdx, gdy, th, thd);
         if (a.status)
             a.status[agent] |= (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) |
                                (thmax < sw::kAngleLimit ? 0 : SW_STATUS_RANGE) | (sim_ok ? 0 : SW_STATUS_PARAM);

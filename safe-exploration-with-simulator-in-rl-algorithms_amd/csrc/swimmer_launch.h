@@ -79,6 +79,8 @@
 //   swimmer_cov.hip, swimmer_cov.h
 //   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound; its tile code
 //                              (swimmer_cov.h) also rides along in the segment-per-lane rollout launches (SideJob)
+//   swimmer_cacla_learner.h     the CACLA learner of the two files below: the layout of an agent's networks over its
+//                              wave, weight / state / noise loads and stores, forward<N> and learn<N>
 //   swimmer_cacla.hip (a translation unit of its own)
 //   cacla_kernel<N,TRAIN>      sw_cacla_run_f64: CACLA training runs of many independent agents, n_iter sequential
 //                              steps in one launch, ONE WAVE PER AGENT: the agent's n two-layer networks in registers
@@ -87,7 +89,7 @@
 //                              with v_readlane; instruction-issue bound like the latency forms
 //   swimmer_cacla_safe.hip (a translation unit of its own)
 //   cacla_safe_kernel<N>       sw_cacla_safe_run_f64: the same learner behind a per-step simulator gate, per agent gated
-//                              or not: cacla_kernel's layout and arithmetic (an ungated agent has its bits), plus the
+//                              or not: cacla_kernel's learner in its order (an ungated agent has its bits), plus the
 //                              simulator's look-ahead step and the cost redundantly in every lane, the admit decision
 //                              taken from the first lane into a scalar register, the real step and the update behind
 //                              a uniform branch; reward entry and admit flag staged per lane, stored once per block
