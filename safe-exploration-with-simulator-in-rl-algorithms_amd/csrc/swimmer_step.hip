@@ -1,6 +1,16 @@
 // swimmer_step.hip -- one physics step for a batch of environments: step / accelerations / reset, the estimator's
 // residual kernels (one parameter set, a population, or populations over many transition sets), the batch-1 environment (sw_env1), and their entry points.
+//
+// The kernels are put together from ONE copy of each piece, __device__ __forceinline__ function templates over arrays
+// that stay plain locals of the kernels (a struct that owns the arrays costs registers, DESIGN.md "One learner, two
+// kernels"): load_state / load_action / store_state and load_transition (the SoA columns), step_checked and
+// accel_checked (the step and the accelerations with their NaN rules), residual_sq (the distance to the stored next
+// state), wave_sum / post_wave_sum / waves_in_order / row_sum (the fixed-order sums), candidate_setup and
+// score_candidates (a candidate's consts and the candidate loop).  What the tests promise bit for bit -- population
+// and sets against the single kernel, env1 against the batched kernels, the row sums' order -- holds because these
+// are the same functions, not because copies are kept in step.
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "swimmer_launch.h"
@@ -21,29 +31,87 @@ template <bool NT> __device__ __forceinline__ void st_f64(double v, double *p)
     if (NT) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
-#define SW_LD(p) ld_f64<NT>(p)
-#define SW_ST(v, p) st_f64<NT>(v, p)
 
-template <int N, bool TWIN, bool NT>
-__global__ void __launch_bounds__(kStepBlock)
-step_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restrict__ sin_,
-            const double *__restrict__ act, double *__restrict__ sout,
-            double *__restrict__ reward, int32_t *__restrict__ status)
+// Column e of a state array [2 + 2 N][n_env]: Gdot, then theta_i, thetadot_i.  The column's pointer is formed first
+// and the rows are steps of n_env from it: with the row's offset multiplied out per element the plain kernels get
+// 64-bit multiply-adds for what are chained adds here.
+template <int N, bool NT>
+__device__ __forceinline__ void load_state(const double *__restrict__ s, int64_t n_env, int64_t e, double &gdx,
+                                           double &gdy, double (&th)[N], double (&thd)[N])
 {
-    constexpr int M = N - 1;
-    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
-    if (e >= n_env) return;
-    double gdx = SW_LD(&sin_[e]), gdy = SW_LD(&sin_[n_env + e]);
-    double th[N], thd[N], u[M];
+    const double *col = s + e;
+    gdx = ld_f64<NT>(col);
+    gdy = ld_f64<NT>(col + n_env);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
-        thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
+        th[i] = ld_f64<NT>(col + (int64_t)(2 + 2 * i) * n_env);
+        thd[i] = ld_f64<NT>(col + (int64_t)(3 + 2 * i) * n_env);
     }
+}
+
+template <int N, bool NT>
+__device__ __forceinline__ void load_action(const double *__restrict__ act, int64_t n_env, int64_t e,
+                                            double (&u)[N - 1])
+{
+    const double *col = act + e;
 #pragma unroll
-    for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
-    double r;
-    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+    for (int i = 0; i < N - 1; ++i) u[i] = ld_f64<NT>(col + (int64_t)i * n_env);
+}
+
+// Stores the column and returns SW_STATUS_NONFINITE unless every entry of it is finite (else 0).
+template <int N, bool NT>
+__device__ __forceinline__ int32_t store_state(double *__restrict__ s, int64_t n_env, int64_t e, double gdx, double gdy,
+                                               const double (&th)[N], const double (&thd)[N])
+{
+    double *col = s + e;
+    st_f64<NT>(gdx, col);
+    st_f64<NT>(gdy, col + n_env);
+    bool fin = isfinite(gdx) && isfinite(gdy);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        st_f64<NT>(th[i], col + (int64_t)(2 + 2 * i) * n_env);
+        st_f64<NT>(thd[i], col + (int64_t)(3 + 2 * i) * n_env);
+        fin = fin && isfinite(th[i]) && isfinite(thd[i]);
+    }
+    return fin ? 0 : SW_STATUS_NONFINITE;
+}
+
+// Workgroups of kStepBlock that cover n transitions (environments): the grid, and the length of a row of partials.
+__host__ __device__ inline int64_t step_blocks(int64_t n) { return n <= 0 ? 0 : (n + kStepBlock - 1) / kStepBlock; }
+
+// A stored transition: state, action and the stored next state (whose loads are in flight while the step is
+// computed).  A lane that holds no transition (!live) gets zeros and reads nothing.
+template <int N, bool NT>
+__device__ __forceinline__ void load_transition(bool live, int64_t n_env, int64_t e, const double *__restrict__ sin_,
+                                                const double *__restrict__ act, const double *__restrict__ next_ref,
+                                                double &gdx, double &gdy, double (&th)[N], double (&thd)[N],
+                                                double (&u)[N - 1], double &rx, double &ry, double (&rth)[N],
+                                                double (&rthd)[N])
+{
+    gdx = gdy = rx = ry = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) th[i] = thd[i] = rth[i] = rthd[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < N - 1; ++i) u[i] = 0.0;
+    if (live) {
+        load_state<N, NT>(sin_, n_env, e, gdx, gdy, th, thd);
+        load_action<N, NT>(act, n_env, e, u);
+        load_state<N, NT>(next_ref, n_env, e, rx, ry, rth, rthd);
+    }
+}
+
+// Inside sincos_fast's range?  Outside it every result is NaN (SW_STATUS_RANGE where there is a status).
+template <int N> __device__ __forceinline__ bool angles_in_range(const double (&th)[N])
+{
+    return sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+}
+
+// One step in place with the range rule; returns the status word but for SW_STATUS_NONFINITE, which store_state adds.
+template <int N, bool TWIN>
+__device__ __forceinline__ int32_t step_checked(const sw::Consts &C, const sw::TwinConsts &T, double &gdx, double &gdy,
+                                                double (&th)[N], double (&thd)[N], const double (&u)[N - 1], double &r)
+{
+    const bool in_range = angles_in_range<N>(th);
     const bool ok = TWIN ? sw::twin_step<N>(T, gdx, gdy, th, thd, u, r)
                          : sw::euler_step<N>(C, gdx, gdy, th, thd, u, r);
     if (!in_range) {   // outside sincos_fast's range: NaN out, SW_STATUS_RANGE
@@ -51,19 +119,123 @@ step_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restr
 #pragma unroll
         for (int i = 0; i < N; ++i) th[i] = thd[i] = __builtin_nan("");
     }
-    SW_ST(gdx, &sout[e]);
-    SW_ST(gdy, &sout[n_env + e]);
-    bool fin = isfinite(gdx) && isfinite(gdy);
+    return (ok ? 0 : SW_STATUS_SINGULAR) | (in_range ? 0 : SW_STATUS_RANGE);
+}
+
+// The accelerations with the range rule.
+template <int N, bool TWIN>
+__device__ __forceinline__ void accel_checked(const sw::Consts &C, const sw::TwinConsts &T, double gdx, double gdy,
+                                              const double (&th)[N], const double (&thd)[N], const double (&u)[N - 1],
+                                              double &ax, double &ay, double (&a)[N])
+{
+    const bool in_range = angles_in_range<N>(th);
+    if (TWIN) sw::accelerations_twin<N>(T, gdx, gdy, th, thd, u, ax, ay, a);
+    else sw::accelerations<N>(C, gdx, gdy, th, thd, u, ax, ay, a);
+    if (!in_range) {
+        ax = ay = __builtin_nan("");
+#pragma unroll
+        for (int i = 0; i < N; ++i) a[i] = __builtin_nan("");
+    }
+}
+
+// || state - stored next state ||^2: one product, then an FMA chain over the components in the state's order.
+template <int N>
+__device__ __forceinline__ double residual_sq(double gdx, double gdy, const double (&th)[N], const double (&thd)[N],
+                                              double rx, double ry, const double (&rth)[N], const double (&rthd)[N])
+{
+    double q = (gdx - rx) * (gdx - rx);
+    q = __builtin_fma(gdy - ry, gdy - ry, q);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        SW_ST(th[i], &sout[(int64_t)(2 + 2 * i) * n_env + e]);
-        SW_ST(thd[i], &sout[(int64_t)(3 + 2 * i) * n_env + e]);
-        fin = fin && isfinite(th[i]) && isfinite(thd[i]);
+        q = __builtin_fma(th[i] - rth[i], th[i] - rth[i], q);
+        q = __builtin_fma(thd[i] - rthd[i], thd[i] - rthd[i], q);
     }
-    if (reward) SW_ST(r, &reward[e]);
-    if (status)
-        status[e] = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) |
-                    (in_range ? 0 : SW_STATUS_RANGE);
+    return q;
+}
+
+// The fixed-order sums.  wave_sum: the 64 lanes by shuffle tree (lane 0 has the sum).  post_wave_sum: a workgroup's
+// value goes to w[wave]; behind a barrier waves_in_order adds those left to right.  row_sum: lane l adds
+// row[l], row[l + 64], ... in turn (starting from 0.0), then the 64 lane sums go through the tree.
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;
+}
+
+__device__ __forceinline__ void post_wave_sum(double v, double *w)
+{
+    v = wave_sum(v);
+    if (threadIdx.x % kWave == 0) w[threadIdx.x / kWave] = v;
+}
+
+__device__ __forceinline__ double waves_in_order(const double *w)
+{
+    double t = w[0];
+#pragma unroll
+    for (int i = 1; i < kStepBlock / kWave; ++i) t += w[i];
+    return t;
+}
+
+__device__ __forceinline__ double row_sum(const double *__restrict__ row, int64_t nb)
+{
+    double t = 0.0;
+    for (int64_t b = threadIdx.x; b < nb; b += kWave) t += row[b];
+    return wave_sum(t);
+}
+
+// A candidate x = [l_i, m_i, k] on top of the base parameters' h and direction: its consts, and whether it keeps
+// validate_params' rule (a candidate that does not scores NaN, SW_STATUS_PARAM).
+template <int N>
+__device__ __forceinline__ bool candidate_setup(const sw::Consts &base, const double *__restrict__ x, sw::Consts &c)
+{
+    const double l = x[0], m = x[1], k = x[2];
+    c = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
+    return sim_params_ok(l, m, k);
+}
+
+// Candidates [c, c1) scored on the transition this lane holds: per candidate a copy of the state is stepped and
+// its distance summed over the workgroup's waves into wsum[k] -- everything step_residual_kernel does for one.
+template <int N>
+__device__ __forceinline__ void score_candidates(int c, int c1, const sw::Consts *cc, const int *cok, bool live,
+                                                 bool in_range, double gdx, double gdy, const double (&th)[N],
+                                                 const double (&thd)[N], const double (&u)[N - 1], double rx,
+                                                 double ry, const double (&rth)[N], const double (&rthd)[N],
+                                                 double (*wsum)[kStepBlock / kWave])
+{
+#pragma unroll 1
+    for (int k = c; k < c1; ++k) {
+        double dist = 0.0;
+        if (live) {
+            double x = gdx, y = gdy, t[N], td[N], r;
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                t[i] = th[i];
+                td[i] = thd[i];
+            }
+            (void)sw::euler_step<N>(cc[k], x, y, t, td, u, r);
+            const double q = residual_sq<N>(x, y, t, td, rx, ry, rth, rthd);
+            dist = (in_range && cok[k]) ? sqrt(q) : __builtin_nan("");
+        }
+        post_wave_sum(dist, wsum[k]);
+    }
+}
+
+template <int N, bool TWIN, bool NT>
+__global__ void __launch_bounds__(kStepBlock)
+step_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restrict__ sin_,
+            const double *__restrict__ act, double *__restrict__ sout,
+            double *__restrict__ reward, int32_t *__restrict__ status)
+{
+    const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    if (e >= n_env) return;
+    double gdx, gdy, th[N], thd[N], u[N - 1], r;
+    load_state<N, NT>(sin_, n_env, e, gdx, gdy, th, thd);
+    load_action<N, NT>(act, n_env, e, u);
+    int32_t word = step_checked<N, TWIN>(C, T, gdx, gdy, th, thd, u, r);
+    word |= store_state<N, NT>(sout, n_env, e, gdx, gdy, th, thd);
+    if (reward) st_f64<NT>(r, &reward[e]);
+    if (status) status[e] = word;
 }
 
 // One physics step per stored transition, COMPARED with the stored next state instead of written out: the
@@ -77,49 +249,20 @@ __global__ void __launch_bounds__(kStepBlock)
 step_residual_kernel(sw::Consts C, int64_t n_env, const double *__restrict__ sin_, const double *__restrict__ act,
                      const double *__restrict__ next_ref, double *__restrict__ partial)
 {
-    constexpr int M = N - 1;
     __shared__ double wsum[kStepBlock / kWave];
     const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
     double dist = 0.0;
     if (e < n_env) {
-        double gdx = SW_LD(&sin_[e]), gdy = SW_LD(&sin_[n_env + e]);
-        double th[N], thd[N], u[M];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
-            thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
-        }
-#pragma unroll
-        for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
-        // the stored next state: its loads are in flight while the step is computed
-        double rx = SW_LD(&next_ref[e]), ry = SW_LD(&next_ref[n_env + e]), rth[N], rthd[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            rth[i] = SW_LD(&next_ref[(int64_t)(2 + 2 * i) * n_env + e]);
-            rthd[i] = SW_LD(&next_ref[(int64_t)(3 + 2 * i) * n_env + e]);
-        }
-        const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
-        double r;
+        double gdx, gdy, th[N], thd[N], u[N - 1], rx, ry, rth[N], rthd[N], r;
+        load_transition<N, NT>(true, n_env, e, sin_, act, next_ref, gdx, gdy, th, thd, u, rx, ry, rth, rthd);
+        const bool in_range = angles_in_range<N>(th);
         (void)sw::euler_step<N>(C, gdx, gdy, th, thd, u, r);
-        double q = (gdx - rx) * (gdx - rx);
-        q = __builtin_fma(gdy - ry, gdy - ry, q);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            q = __builtin_fma(th[i] - rth[i], th[i] - rth[i], q);
-            q = __builtin_fma(thd[i] - rthd[i], thd[i] - rthd[i], q);
-        }
+        const double q = residual_sq<N>(gdx, gdy, th, thd, rx, ry, rth, rthd);
         dist = in_range ? sqrt(q) : __builtin_nan("");
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
-    if (threadIdx.x % kWave == 0) wsum[threadIdx.x / kWave] = dist;
+    post_wave_sum(dist, wsum);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = wsum[0];
-#pragma unroll
-        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[w];
-        partial[blockIdx.x] = t;
-    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = waves_in_order(wsum);
 }
 
 // The same objective for a POPULATION of parameter sets (the CMA-ES generation of the estimator's search): each
@@ -135,90 +278,33 @@ step_residual_pop_kernel(sw::Consts base, int64_t n_cand, const double *__restri
                          const double *__restrict__ next_ref, double *__restrict__ partial,
                          int32_t *__restrict__ cand_status)
 {
-    constexpr int M = N - 1;
     __shared__ sw::Consts cc[kPopGroup];
     __shared__ int cok[kPopGroup];
     __shared__ double wsum[kPopGroup][kStepBlock / kWave];
     const int64_t j0 = (int64_t)blockIdx.y * kPopGroup;
     const int nc = (int)(n_cand - j0 < kPopGroup ? n_cand - j0 : kPopGroup);
     if ((int)threadIdx.x < nc) {
-        const double *x = cand + (j0 + threadIdx.x) * 3;   // [l_i, m_i, k]
-        const double l = x[0], m = x[1], k = x[2];
-        const bool ok = l > 0.0 && m > 0.0 && isfinite(l) && isfinite(m) && isfinite(k);
-        cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
+        const bool ok = candidate_setup<N>(base, cand + (j0 + threadIdx.x) * 3, cc[threadIdx.x]);
         cok[threadIdx.x] = ok;
         if (cand_status && blockIdx.x == 0) cand_status[j0 + threadIdx.x] = ok ? SW_STATUS_OK : SW_STATUS_PARAM;
     }
     const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
     const bool live = e < n_env;
-    double gdx = 0.0, gdy = 0.0, th[N], thd[N], u[M], rx = 0.0, ry = 0.0, rth[N], rthd[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) th[i] = thd[i] = rth[i] = rthd[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) u[i] = 0.0;
-    if (live) {
-        gdx = SW_LD(&sin_[e]);
-        gdy = SW_LD(&sin_[n_env + e]);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            th[i] = SW_LD(&sin_[(int64_t)(2 + 2 * i) * n_env + e]);
-            thd[i] = SW_LD(&sin_[(int64_t)(3 + 2 * i) * n_env + e]);
-        }
-#pragma unroll
-        for (int i = 0; i < M; ++i) u[i] = SW_LD(&act[(int64_t)i * n_env + e]);
-        rx = SW_LD(&next_ref[e]);
-        ry = SW_LD(&next_ref[n_env + e]);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            rth[i] = SW_LD(&next_ref[(int64_t)(2 + 2 * i) * n_env + e]);
-            rthd[i] = SW_LD(&next_ref[(int64_t)(3 + 2 * i) * n_env + e]);
-        }
-    }
-    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
+    double gdx, gdy, th[N], thd[N], u[N - 1], rx, ry, rth[N], rthd[N];
+    load_transition<N, NT>(live, n_env, e, sin_, act, next_ref, gdx, gdy, th, thd, u, rx, ry, rth, rthd);
+    const bool in_range = angles_in_range<N>(th);
     __syncthreads();
-#pragma unroll 1
-    for (int c = 0; c < nc; ++c) {
-        double dist = 0.0;
-        if (live) {
-            double x = gdx, y = gdy, t[N], td[N], r;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                t[i] = th[i];
-                td[i] = thd[i];
-            }
-            (void)sw::euler_step<N>(cc[c], x, y, t, td, u, r);
-            double q = (x - rx) * (x - rx);
-            q = __builtin_fma(y - ry, y - ry, q);
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                q = __builtin_fma(t[i] - rth[i], t[i] - rth[i], q);
-                q = __builtin_fma(td[i] - rthd[i], td[i] - rthd[i], q);
-            }
-            dist = (in_range && cok[c]) ? sqrt(q) : __builtin_nan("");
-        }
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
-        if (threadIdx.x % kWave == 0) wsum[c][threadIdx.x / kWave] = dist;
-    }
+    score_candidates<N>(0, nc, cc, cok, live, in_range, gdx, gdy, th, thd, u, rx, ry, rth, rthd, wsum);
     __syncthreads();
-    if ((int)threadIdx.x < nc) {
-        double t = wsum[threadIdx.x][0];
-#pragma unroll
-        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
-        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
-    }
+    if ((int)threadIdx.x < nc)
+        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = waves_in_order(wsum[threadIdx.x]);
 }
 
-// value[j] = the sum of row j of partial [n_cand][nb] in ONE fixed order: lane l adds b = l, l + 64, l + 128, ... in
-// turn (starting from 0.0), then the 64 lane sums go through the shuffle tree.  One wave per candidate.
+// value[j] = the sum of row j of partial [n_cand][nb] in row_sum's order.  One wave per candidate.
 __global__ void __launch_bounds__(kWave)
 residual_rows_sum_kernel(int64_t nb, const double *__restrict__ partial, double *__restrict__ value)
 {
-    const double *row = partial + (int64_t)blockIdx.x * nb;
-    double t = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += kWave) t += row[b];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) t += __shfl_down(t, off, kWave);
+    const double t = row_sum(partial + (int64_t)blockIdx.x * nb, nb);
     if (threadIdx.x == 0) value[blockIdx.x] = t;
 }
 
@@ -252,7 +338,6 @@ step_residual_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *__restr
                           const double *__restrict__ next_ref, double *__restrict__ partial,
                           int32_t *__restrict__ cand_status)
 {
-    constexpr int M = N - 1;
     __shared__ sw::Consts cc[kPopGroup];
     __shared__ int cok[kPopGroup];
     __shared__ int64_t cbeg[kPopGroup], clen[kPopGroup];
@@ -268,19 +353,13 @@ step_residual_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *__restr
         longest = len > longest ? len : longest;
     }
     if ((int)threadIdx.x < nc) {
-        const double *x = cand + (j0 + threadIdx.x) * 3;   // [l_i, m_i, k]
-        const double l = x[0], m = x[1], k = x[2];
-        const bool ok = sim_params_ok(l, m, k);
+        const bool ok = candidate_setup<N>(base, cand + (j0 + threadIdx.x) * 3, cc[threadIdx.x]);
+        cok[threadIdx.x] = ok;
         if (cand_status && blockIdx.x == 0) cand_status[j0 + threadIdx.x] = ok ? SW_STATUS_OK : SW_STATUS_PARAM;
         if (t0 < longest) {
-            int64_t b0, len;
             const int32_t s = cand_set[j0 + threadIdx.x];
-            (void)set_span(set_begin, s, n_set, n_env, max_set_len, b0, len);
-            cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
-            cok[threadIdx.x] = ok;
             cset[threadIdx.x] = s;
-            cbeg[threadIdx.x] = b0;
-            clen[threadIdx.x] = len;
+            (void)set_span(set_begin, s, n_set, n_env, max_set_len, cbeg[threadIdx.x], clen[threadIdx.x]);
         }
     }
     if (t0 >= longest) return;   // beyond every set of this group (uniform, in front of the barriers)
@@ -289,73 +368,25 @@ step_residual_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *__restr
     while (c < nc) {             // one trip per run of same-set candidates (uniform)
         int c1 = c + 1;
         while (c1 < nc && cset[c1] == cset[c]) ++c1;
-        const int64_t b0 = cbeg[c], len = clen[c];
+        const int64_t len = clen[c];
         if (t0 < len) {
             const bool live = t0 + threadIdx.x < len;
-            const int64_t e = b0 + t0 + threadIdx.x;
-            double gdx = 0.0, gdy = 0.0, th[N], thd[N], u[M], rx = 0.0, ry = 0.0, rth[N], rthd[N];
-#pragma unroll
-            for (int i = 0; i < N; ++i) th[i] = thd[i] = rth[i] = rthd[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < M; ++i) u[i] = 0.0;
-            if (live) {
-                gdx = sin_[e];
-                gdy = sin_[n_env + e];
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-                    th[i] = sin_[(int64_t)(2 + 2 * i) * n_env + e];
-                    thd[i] = sin_[(int64_t)(3 + 2 * i) * n_env + e];
-                }
-#pragma unroll
-                for (int i = 0; i < M; ++i) u[i] = act[(int64_t)i * n_env + e];
-                rx = next_ref[e];
-                ry = next_ref[n_env + e];
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-                    rth[i] = next_ref[(int64_t)(2 + 2 * i) * n_env + e];
-                    rthd[i] = next_ref[(int64_t)(3 + 2 * i) * n_env + e];
-                }
-            }
-            const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
-#pragma unroll 1
-            for (int k = c; k < c1; ++k) {
-                double dist = 0.0;
-                if (live) {
-                    double x = gdx, y = gdy, t[N], td[N], r;
-#pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        t[i] = th[i];
-                        td[i] = thd[i];
-                    }
-                    (void)sw::euler_step<N>(cc[k], x, y, t, td, u, r);
-                    double q = (x - rx) * (x - rx);
-                    q = __builtin_fma(y - ry, y - ry, q);
-#pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        q = __builtin_fma(t[i] - rth[i], t[i] - rth[i], q);
-                        q = __builtin_fma(td[i] - rthd[i], td[i] - rthd[i], q);
-                    }
-                    dist = (in_range && cok[k]) ? sqrt(q) : __builtin_nan("");
-                }
-#pragma unroll
-                for (int off = kWave / 2; off > 0; off >>= 1) dist += __shfl_down(dist, off, kWave);
-                if (threadIdx.x % kWave == 0) wsum[k][threadIdx.x / kWave] = dist;
-            }
+            double gdx, gdy, th[N], thd[N], u[N - 1], rx, ry, rth[N], rthd[N];
+            load_transition<N, false>(live, n_env, cbeg[c] + t0 + threadIdx.x, sin_, act, next_ref, gdx, gdy, th, thd,
+                                      u, rx, ry, rth, rthd);
+            score_candidates<N>(c, c1, cc, cok, live, angles_in_range<N>(th), gdx, gdy, th, thd, u, rx, ry, rth, rthd,
+                                wsum);
         }
         c = c1;
     }
     __syncthreads();
-    if ((int)threadIdx.x < nc && t0 < clen[threadIdx.x]) {
-        double t = wsum[threadIdx.x][0];
-#pragma unroll
-        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
-        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
-    }
+    if ((int)threadIdx.x < nc && t0 < clen[threadIdx.x])
+        partial[(j0 + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = waves_in_order(wsum[threadIdx.x]);
 }
 
 // residual_rows_sum_kernel for rows of different lengths: row r of partial [gridDim.x][stride] belongs to set
 // row_set[r] (nullptr: to set r / rows_per_set) and holds one entry per 256-transition block of that set; value[r] =
-// their sum in residual_rows_sum_kernel's order.  A set with active[s] == 0, or with bounds that do not fit, is skipped.
+// their sum in row_sum's order.  A set with active[s] == 0, or with bounds that do not fit, is skipped.
 __global__ void __launch_bounds__(kWave)
 residual_set_rows_sum_kernel(int64_t n_set, const int64_t *__restrict__ set_begin, int64_t max_set_len, int64_t n_env,
                              const int32_t *__restrict__ row_set, int rows_per_set, const int32_t *__restrict__ active,
@@ -365,12 +396,7 @@ residual_set_rows_sum_kernel(int64_t n_set, const int64_t *__restrict__ set_begi
     int64_t b0, len;
     if (!set_span(set_begin, s, n_set, n_env, max_set_len, b0, len)) return;
     if (active && !active[s]) return;
-    const int64_t nb = (len + kStepBlock - 1) / kStepBlock;
-    const double *row = partial + (int64_t)blockIdx.x * stride;
-    double t = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += kWave) t += row[b];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) t += __shfl_down(t, off, kWave);
+    const double t = row_sum(partial + (int64_t)blockIdx.x * stride, step_blocks(len));
     if (threadIdx.x == 0) value[blockIdx.x] = t;
 }
 
@@ -390,7 +416,7 @@ step_residual_normal_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *
                                  const double *__restrict__ next_ref, double *__restrict__ partial,
                                  int32_t *__restrict__ set_status)
 {
-    constexpr int M = N - 1, D = 2 * N + 2, K = NP == 7 ? 13 : 1;
+    constexpr int D = 2 * N + 2, K = NP == 7 ? 13 : 1;
     static_assert(NP == 1 || NP == 7, "one point (cost) or seven (normal equations)");
     __shared__ sw::Consts cc[NP];
     __shared__ int cok[NP];
@@ -400,31 +426,13 @@ step_residual_normal_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *
     if (!set_span(set_begin, s, n_set, n_env, max_set_len, b0, len)) return;   // uniform, in front of the barriers
     if (active && !active[s]) return;
     if (t0 >= len) return;
-    if ((int)threadIdx.x < NP) {
-        const double *x = points + (s * NP + threadIdx.x) * 3;
-        const double l = x[0], m = x[1], k = x[2];
-        cc[threadIdx.x] = sw::consts_of(N, l, m, k, base.h, base.dirx, base.diry);
-        cok[threadIdx.x] = sim_params_ok(l, m, k);
-    }
+    if ((int)threadIdx.x < NP)
+        cok[threadIdx.x] = candidate_setup<N>(base, points + (s * NP + threadIdx.x) * 3, cc[threadIdx.x]);
     const bool live = t0 + threadIdx.x < len;
-    const int64_t e = b0 + t0 + threadIdx.x;
-    double st[D], ref[D], u[M];
-#pragma unroll
-    for (int i = 0; i < D; ++i) st[i] = ref[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) u[i] = 0.0;
-    if (live) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) st[i] = sin_[(int64_t)i * n_env + e];
-#pragma unroll
-        for (int i = 0; i < M; ++i) u[i] = act[(int64_t)i * n_env + e];
-#pragma unroll
-        for (int i = 0; i < D; ++i) ref[i] = next_ref[(int64_t)i * n_env + e];
-    }
-    double th0[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) th0[i] = st[2 + 2 * i];
-    const bool in_range = sw::track_angle_range<N>(0.0, th0) < sw::kAngleLimit;
+    double gdx, gdy, th[N], thd[N], u[N - 1], rx, ry, rth[N], rthd[N];
+    load_transition<N, false>(live, n_env, b0 + t0 + threadIdx.x, sin_, act, next_ref, gdx, gdy, th, thd, u, rx, ry,
+                              rth, rthd);
+    const bool in_range = angles_in_range<N>(th);
     double ie[3] = {0.0, 0.0, 0.0};
     if (NP == 7) {
 #pragma unroll
@@ -437,20 +445,20 @@ step_residual_normal_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *
     for (int i = 0; i < D; ++i) r0[i] = rp[i] = J0[i] = J1[i] = J2[i] = 0.0;
 #pragma unroll 1
     for (int p = 0; p < NP; ++p) {   // one copy of the step's code; the point's role is a uniform choice
-        double x = st[0], y = st[1], t[N], td[N], rew, rt[D];
+        double x = gdx, y = gdy, t[N], td[N], rew, rt[D];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            t[i] = st[2 + 2 * i];
-            td[i] = st[3 + 2 * i];
+            t[i] = th[i];
+            td[i] = thd[i];
         }
         (void)sw::euler_step<N>(cc[p], x, y, t, td, u, rew);
         ok = ok && cok[p];
-        rt[0] = x - ref[0];
-        rt[1] = y - ref[1];
+        rt[0] = x - rx;
+        rt[1] = y - ry;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            rt[2 + 2 * i] = t[i] - ref[2 + 2 * i];
-            rt[3 + 2 * i] = td[i] - ref[3 + 2 * i];
+            rt[2 + 2 * i] = t[i] - rth[i];
+            rt[3 + 2 * i] = td[i] - rthd[i];
         }
         if (p == 0) {
 #pragma unroll
@@ -493,19 +501,10 @@ step_residual_normal_sets_kernel(sw::Consts base, int64_t n_set, const int64_t *
         acc[8] = acc[6];
     }
 #pragma unroll
-    for (int v = 0; v < K; ++v) {
-        double a = live ? (ok ? acc[v] : __builtin_nan("")) : 0.0;
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) a += __shfl_down(a, off, kWave);
-        if (threadIdx.x % kWave == 0) wsum[v][threadIdx.x / kWave] = a;
-    }
+    for (int v = 0; v < K; ++v) post_wave_sum(live ? (ok ? acc[v] : __builtin_nan("")) : 0.0, wsum[v]);
     __syncthreads();
-    if ((int)threadIdx.x < K) {
-        double t = wsum[threadIdx.x][0];
-#pragma unroll
-        for (int w = 1; w < kStepBlock / kWave; ++w) t += wsum[threadIdx.x][w];
-        partial[(s * K + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = t;
-    }
+    if ((int)threadIdx.x < K)
+        partial[(s * K + threadIdx.x) * (int64_t)gridDim.x + blockIdx.x] = waves_in_order(wsum[threadIdx.x]);
     if (set_status && blockIdx.x == 0 && threadIdx.x == 0) {
         bool all = true;
         for (int p = 0; p < NP; ++p) all = all && cok[p];
@@ -518,25 +517,12 @@ __global__ void __launch_bounds__(kStepBlock)
 accel_kernel(sw::Consts C, sw::TwinConsts T, int64_t n_env, const double *__restrict__ sin_,
              const double *__restrict__ act, double *__restrict__ gdd, double *__restrict__ tdd)
 {
-    constexpr int M = N - 1;
     const int64_t e = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
     if (e >= n_env) return;
-    double gdx = sin_[e], gdy = sin_[n_env + e];
-    double th[N], thd[N], u[M], a[N], ax, ay;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        th[i] = sin_[(int64_t)(2 + 2 * i) * n_env + e];
-        thd[i] = sin_[(int64_t)(3 + 2 * i) * n_env + e];
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) u[i] = act[(int64_t)i * n_env + e];
-    if (TWIN) sw::accelerations_twin<N>(T, gdx, gdy, th, thd, u, ax, ay, a);
-    else sw::accelerations<N>(C, gdx, gdy, th, thd, u, ax, ay, a);
-    if (!(sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit)) {
-        ax = ay = __builtin_nan("");
-#pragma unroll
-        for (int i = 0; i < N; ++i) a[i] = __builtin_nan("");
-    }
+    double gdx, gdy, th[N], thd[N], u[N - 1], a[N], ax, ay;
+    load_state<N, false>(sin_, n_env, e, gdx, gdy, th, thd);
+    load_action<N, false>(act, n_env, e, u);
+    accel_checked<N, TWIN>(C, T, gdx, gdy, th, thd, u, ax, ay, a);
     gdd[e] = ax;
     gdd[n_env + e] = ay;
 #pragma unroll
@@ -560,8 +546,8 @@ __global__ void reset_kernel(int n, int twin, int64_t n_env, double *__restrict_
 // One swimmer handed over in HOST memory (sw_env1, the batch-1 drop-in surfaces).  io = the
 // handle's pinned, device-mapped block (SW_ENV1_* offsets).  One wave: lane l pulls double l of
 // [state | action] -- ONE read burst over the bus instead of 25 round trips -- every lane then
-// runs the same step on broadcast copies, lane 0 posts the results and, behind a system-scope
-// fence, the sequence number the host spins on.
+// runs the same step on broadcast copies (step_checked / accel_checked: the batched kernels' bits), lane 0 posts
+// the results and, behind a system-scope fence, the sequence number the host spins on.
 template <int N, bool TWIN, bool ACCEL>
 __global__ void __launch_bounds__(kWave)
 env1_kernel(sw::Consts C, sw::TwinConsts T, double *__restrict__ io, int32_t *__restrict__ status,
@@ -571,7 +557,7 @@ env1_kernel(sw::Consts C, sw::TwinConsts T, double *__restrict__ io, int32_t *__
     const int lane = threadIdx.x;
     const double mine = (lane < SW_ENV1_ACTION + M) ? io[lane] : 0.0;   // state 0..17, action 18..24
     double gdx = __shfl(mine, 0, kWave), gdy = __shfl(mine, 1, kWave);
-    double th[N], thd[N], u[M > 0 ? M : 1];
+    double th[N], thd[N], u[M];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         th[i] = __shfl(mine, 2 + 2 * i, kWave);
@@ -579,40 +565,21 @@ env1_kernel(sw::Consts C, sw::TwinConsts T, double *__restrict__ io, int32_t *__
     }
 #pragma unroll
     for (int i = 0; i < M; ++i) u[i] = __shfl(mine, SW_ENV1_ACTION + i, kWave);
-    const bool in_range = sw::track_angle_range<N>(0.0, th) < sw::kAngleLimit;
     if (ACCEL) {
         double ax, ay, a[N];
-        if (TWIN) sw::accelerations_twin<N>(T, gdx, gdy, th, thd, u, ax, ay, a);
-        else sw::accelerations<N>(C, gdx, gdy, th, thd, u, ax, ay, a);
+        accel_checked<N, TWIN>(C, T, gdx, gdy, th, thd, u, ax, ay, a);
         if (lane == 0) {
-            io[SW_ENV1_GDD] = in_range ? ax : __builtin_nan("");
-            io[SW_ENV1_GDD + 1] = in_range ? ay : __builtin_nan("");
+            io[SW_ENV1_GDD] = ax;
+            io[SW_ENV1_GDD + 1] = ay;
 #pragma unroll
-            for (int i = 0; i < N; ++i) io[SW_ENV1_TDD + i] = in_range ? a[i] : __builtin_nan("");
+            for (int i = 0; i < N; ++i) io[SW_ENV1_TDD + i] = a[i];
         }
     } else {
         double r;
-        const bool ok = TWIN ? sw::twin_step<N>(T, gdx, gdy, th, thd, u, r)
-                             : sw::euler_step<N>(C, gdx, gdy, th, thd, u, r);
-        if (!in_range) {
-            gdx = gdy = r = __builtin_nan("");
-#pragma unroll
-            for (int i = 0; i < N; ++i) th[i] = thd[i] = __builtin_nan("");
-        }
-        bool fin = isfinite(gdx) && isfinite(gdy);
-#pragma unroll
-        for (int i = 0; i < N; ++i) fin = fin && isfinite(th[i]) && isfinite(thd[i]);
-        if (lane == 0) {
-            io[SW_ENV1_NEXT] = gdx;
-            io[SW_ENV1_NEXT + 1] = gdy;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                io[SW_ENV1_NEXT + 2 + 2 * i] = th[i];
-                io[SW_ENV1_NEXT + 3 + 2 * i] = thd[i];
-            }
+        const int32_t word = step_checked<N, TWIN>(C, T, gdx, gdy, th, thd, u, r);
+        if (lane == 0) {   // the next state is a batch of one: rows at stride 1
+            *status = word | store_state<N, false>(io + SW_ENV1_NEXT, 1, 0, gdx, gdy, th, thd);
             io[SW_ENV1_REWARD] = r;
-            *status = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) |
-                      (in_range ? 0 : SW_STATUS_RANGE);
         }
     }
     static_assert(D <= SW_ENV1_ACTION && SW_ENV1_ACTION + M <= SW_ENV1_NEXT && SW_ENV1_NEXT + D <= SW_ENV1_REWARD,
@@ -628,6 +595,38 @@ bool streams_through_hbm(const sw_params *p, int64_t n_env)
 {
     const int d = 2 * p->n + 2;
     return n_env * (int64_t)(8 * (2 * d + p->n)) > kStepStreamBytes;
+}
+
+bool any_null(std::initializer_list<const void *> pointers)
+{
+    for (const void *p : pointers)
+        if (!p) return true;
+    return false;
+}
+
+// The argument check of the population, sets and normal-equations entries, which all decide in this order: the base
+// parameters (check_params, which also clears stale launch errors), a missing array, a size out of range, then a
+// model or a point count that has no kernel.
+int check_residual_batch(const sw_params *base, bool null_array, bool bad_size, bool bad_choice = false)
+{
+    const int rc = check_params(base);
+    if (rc) return rc;
+    if (null_array) return SW_ERR_NULL;
+    if (bad_size) return SW_ERR_SIZE;
+    return is_twin(base) || bad_choice ? SW_ERR_PARAM : SW_OK;   // the objective is defined on the Gym model
+}
+
+// The end of those entries, behind the launch of the kernel that writes the partials (known_n: with_n found one):
+// its status and, where the caller wants the sums, the launch of the row sums behind it.
+template <class Launch> int then_row_sums(bool known_n, bool wanted, Launch &&launch_row_sums)
+{
+    if (!known_n) return SW_ERR_SEGMENTS;
+    if (wanted) {
+        const int rc = launch_status();
+        if (rc) return rc;
+        launch_row_sums();
+    }
+    return launch_status();
 }
 
 }  // namespace
@@ -656,14 +655,13 @@ int sw_step_f64(const sw_params *p, int64_t n_env, const double *state_in, const
     if (n_env == 0) return SW_OK;
     if (!state_in || !action || !state_out) return SW_ERR_NULL;
     const sw::Consts C = make_consts(p);
-    const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
     const sw::TwinConsts T = make_twin_consts(p);
     bool nt = streams_through_hbm(p, n_env);
     static const char *nt_env = getenv("SWIMMER_STEP_NT");   // measurement knob: "0" / "1" force it
     if (nt_env && (nt_env[0] == '0' || nt_env[0] == '1')) nt = nt_env[0] == '1';
     auto launch = [&](auto *kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kStepBlock), 0, (hipStream_t)stream, C, T, n_env, state_in,
-                           action, state_out, reward, status);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)step_blocks(n_env)), dim3(kStepBlock), 0, (hipStream_t)stream, C, T,
+                           n_env, state_in, action, state_out, reward, status);
     };
     // (the twin model has no nontemporal form)
     const bool known_n =
@@ -682,10 +680,9 @@ int sw_step_residual_f64(const sw_params *p, int64_t n_env, const double *state,
     if (n_env == 0) return SW_OK;
     if (!state || !action || !next_ref || !partial) return SW_ERR_NULL;
     const sw::Consts C = make_consts(p);
-    const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
     const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto NT) {
-        hipLaunchKernelGGL((step_residual_kernel<N.value, NT.value>), dim3(grid), dim3(kStepBlock), 0,
-                           (hipStream_t)stream, C, n_env, state, action, next_ref, partial);
+        hipLaunchKernelGGL((step_residual_kernel<N.value, NT.value>), dim3((unsigned)step_blocks(n_env)),
+                           dim3(kStepBlock), 0, (hipStream_t)stream, C, n_env, state, action, next_ref, partial);
     }, streams_through_hbm(p, n_env));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }
@@ -694,28 +691,22 @@ int sw_step_residual_pop_f64(const sw_params *base, int64_t n_cand, const double
                              const double *state, const double *action, const double *next_ref, double *partial,
                              double *value, int32_t *cand_status, void *stream)
 {
-    int rc = check_params(base);
+    const int rc = check_residual_batch(base, any_null({cand, state, action, next_ref, partial}),
+                                        n_cand < 1 || n_cand > kPopMaxCandidates || n_env < 0);
     if (rc) return rc;
-    if (!cand || !state || !action || !next_ref || !partial) return SW_ERR_NULL;
-    if (n_cand < 1 || n_cand > kPopMaxCandidates || n_env < 0) return SW_ERR_SIZE;
-    if (is_twin(base)) return SW_ERR_PARAM;
     if (n_env == 0) return SW_OK;
     const sw::Consts C = make_consts(base);    // h and the direction; l_i, m_i, k come from each candidate
-    const int64_t nb = (n_env + kStepBlock - 1) / kStepBlock;
+    const int64_t nb = step_blocks(n_env);
     const dim3 grid((unsigned)nb, (unsigned)((n_cand + kPopGroup - 1) / kPopGroup));
     const bool known_n = with_n<2, 8>(base->n, [&](auto N, auto NT) {
         hipLaunchKernelGGL((step_residual_pop_kernel<N.value, NT.value>), grid, dim3(kStepBlock), 0,
                            (hipStream_t)stream, C, n_cand, cand, n_env, state, action, next_ref, partial,
                            cand_status);
     }, streams_through_hbm(base, n_env));
-    if (!known_n) return SW_ERR_SEGMENTS;
-    if (value) {
-        rc = launch_status();
-        if (rc) return rc;
+    return then_row_sums(known_n, value != nullptr, [&] {
         hipLaunchKernelGGL(residual_rows_sum_kernel, dim3((unsigned)n_cand), dim3(kWave), 0, (hipStream_t)stream, nb,
                            partial, value);
-    }
-    return launch_status();
+    });
 }
 
 int sw_step_residual_sets_f64(const sw_params *base, int64_t n_set, const int64_t *set_begin, int64_t max_set_len,
@@ -723,29 +714,23 @@ int sw_step_residual_sets_f64(const sw_params *base, int64_t n_set, const int64_
                               const double *state, const double *action, const double *next_ref, double *partial,
                               double *value, int32_t *cand_status, void *stream)
 {
-    int rc = check_params(base);
+    const int rc = check_residual_batch(base, any_null({set_begin, cand, cand_set, state, action, next_ref, partial}),
+                                        n_set < 1 || n_cand < 1 || n_cand > kPopMaxCandidates || max_set_len < 1 ||
+                                            n_env < 1 || max_set_len > n_env);
     if (rc) return rc;
-    if (!set_begin || !cand || !cand_set || !state || !action || !next_ref || !partial) return SW_ERR_NULL;
-    if (n_set < 1 || n_cand < 1 || n_cand > kPopMaxCandidates || max_set_len < 1 || n_env < 1 || max_set_len > n_env)
-        return SW_ERR_SIZE;
-    if (is_twin(base)) return SW_ERR_PARAM;
     const sw::Consts C = make_consts(base);    // h and the direction; l_i, m_i, k come from each candidate
-    const int64_t nb = (max_set_len + kStepBlock - 1) / kStepBlock;
+    const int64_t nb = step_blocks(max_set_len);
     const dim3 grid((unsigned)nb, (unsigned)((n_cand + kPopGroup - 1) / kPopGroup));
     const bool known_n = with_n<2, 8>(base->n, [&](auto N) {
         hipLaunchKernelGGL((step_residual_sets_kernel<N.value>), grid, dim3(kStepBlock), 0, (hipStream_t)stream, C,
                            n_set, set_begin, max_set_len, n_cand, cand, cand_set, n_env, state, action, next_ref,
                            partial, cand_status);
     });
-    if (!known_n) return SW_ERR_SEGMENTS;
-    if (value) {
-        rc = launch_status();
-        if (rc) return rc;
+    return then_row_sums(known_n, value != nullptr, [&] {
         hipLaunchKernelGGL(residual_set_rows_sum_kernel, dim3((unsigned)n_cand), dim3(kWave), 0, (hipStream_t)stream,
                            n_set, set_begin, max_set_len, n_env, cand_set, 1, (const int32_t *)nullptr, nb, partial,
                            value);
-    }
-    return launch_status();
+    });
 }
 
 int sw_step_residual_normal_sets_f64(const sw_params *base, int64_t n_set, const int64_t *set_begin,
@@ -754,30 +739,28 @@ int sw_step_residual_normal_sets_f64(const sw_params *base, int64_t n_set, const
                                      const double *next_ref, double *partial, double *out, int32_t *set_status,
                                      void *stream)
 {
-    int rc = check_params(base);
+    const int rc = check_residual_batch(
+        base, any_null({set_begin, points, state, action, next_ref, partial, out}) || (n_point == 7 && !inv_2e),
+        n_set < 1 || n_set > kSetsMax || max_set_len < 1 || n_env < 1 || max_set_len > n_env,
+        n_point != 1 && n_point != 7);
     if (rc) return rc;
-    if (!set_begin || !points || !state || !action || !next_ref || !partial || !out) return SW_ERR_NULL;
-    if (n_point == 7 && !inv_2e) return SW_ERR_NULL;
-    if (n_set < 1 || n_set > kSetsMax || max_set_len < 1 || n_env < 1 || max_set_len > n_env) return SW_ERR_SIZE;
-    if (is_twin(base) || (n_point != 1 && n_point != 7)) return SW_ERR_PARAM;
     const sw::Consts C = make_consts(base);
-    const int64_t nb = (max_set_len + kStepBlock - 1) / kStepBlock;
+    const int64_t nb = step_blocks(max_set_len);
     const dim3 grid((unsigned)nb, (unsigned)n_set);
     const bool known_n = with_n<2, 8>(base->n, [&](auto N, auto NORMAL) {
         hipLaunchKernelGGL((step_residual_normal_sets_kernel<N.value, NORMAL.value ? 7 : 1>), grid, dim3(kStepBlock),
                            0, (hipStream_t)stream, C, n_set, set_begin, max_set_len, points, inv_2e, active, n_env,
                            state, action, next_ref, partial, set_status);
     }, n_point == 7);
-    if (!known_n) return SW_ERR_SEGMENTS;
-    rc = launch_status();
-    if (rc) return rc;
     const int K = n_point == 7 ? 13 : 1;
-    hipLaunchKernelGGL(residual_set_rows_sum_kernel, dim3((unsigned)(n_set * K)), dim3(kWave), 0, (hipStream_t)stream,
-                       n_set, set_begin, max_set_len, n_env, (const int32_t *)nullptr, K, active, nb, partial, out);
-    return launch_status();
+    return then_row_sums(known_n, true, [&] {
+        hipLaunchKernelGGL(residual_set_rows_sum_kernel, dim3((unsigned)(n_set * K)), dim3(kWave), 0,
+                           (hipStream_t)stream, n_set, set_begin, max_set_len, n_env, (const int32_t *)nullptr, K,
+                           active, nb, partial, out);
+    });
 }
 
-int64_t sw_step_residual_blocks(int64_t n_env) { return n_env <= 0 ? 0 : (n_env + kStepBlock - 1) / kStepBlock; }
+int64_t sw_step_residual_blocks(int64_t n_env) { return step_blocks(n_env); }
 
 int sw_accel_f64(const sw_params *p, int64_t n_env, const double *state, const double *action,
                  double *gdd, double *tdd, void *stream)
@@ -788,11 +771,10 @@ int sw_accel_f64(const sw_params *p, int64_t n_env, const double *state, const d
     if (n_env == 0) return SW_OK;
     if (!state || !action || !gdd || !tdd) return SW_ERR_NULL;
     const sw::Consts C = make_consts(p);
-    const unsigned grid = (unsigned)((n_env + kStepBlock - 1) / kStepBlock);
     const sw::TwinConsts T = make_twin_consts(p);
     const bool known_n = with_n<2, 8>(p->n, [&](auto N, auto TWIN) {
-        hipLaunchKernelGGL((accel_kernel<N.value, TWIN.value>), dim3(grid), dim3(kStepBlock), 0,
-                           (hipStream_t)stream, C, T, n_env, state, action, gdd, tdd);
+        hipLaunchKernelGGL((accel_kernel<N.value, TWIN.value>), dim3((unsigned)step_blocks(n_env)), dim3(kStepBlock),
+                           0, (hipStream_t)stream, C, T, n_env, state, action, gdd, tdd);
     }, is_twin(p));
     return known_n ? launch_status() : SW_ERR_SEGMENTS;
 }

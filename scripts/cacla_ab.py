@@ -3,8 +3,8 @@ libswimmer_hip.so: are the results the same bits, and is the kernel time the sam
 
     python scripts/cacla_ab.py OLD.so NEW.so [--rounds R] [--timeout SECONDS] [--log FILE]
 
-Per round and library one fresh child process with SWIMMER_HIP_LIB set (OLD, NEW, OLD, NEW, ...), each under its own
-time limit; the script stops at the first child that does not exit 0.  A child
+Per round and library one fresh child process (scripts/ab_common.py has the protocol, the comparison, the noise
+floor and the exit codes).  A child
 
   * runs fixed-seed cases at n = 2 .. 8, 6 agents x 150 steps (two full 64-step noise blocks and a partial one): the
     plain kernel with train on and off, and the gated kernel with gated = [1, 0, 1, 1, 0, 1] behind simulators that
@@ -15,21 +15,14 @@ time limit; the script stops at the first child that does not exit 0.  A child
     the gated kernel with every agent gated and a gate that admits every step (look-ahead, real step and update at
     every step).  Median of 5 after two warm-up launches, with min and max.
 
-The parent compares every array of the two .npz files with np.array_equal (NaNs equal at the same places) and prints
-the timings side by side.  With R > 1 the spread of OLD's medians over the rounds is the noise floor: NEW's median
-of every round has to lie at or below OLD's largest.  Exit status 1: arrays differ; 3: a time above the floor.
-
-Build OLD in a `git worktree` of the parent commit; a library whose sources are newer than it is rebuilt by the test
-suite's conftest (not by this script), so build it last or copy it."""
-import argparse
+The parent compares the arrays bit for bit and the timings against the spread of OLD's medians over the rounds."""
 import json
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import ab_common
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -138,79 +131,8 @@ def child(out_dir):
         json.dump(times, f)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("old")
-    ap.add_argument("new")
-    ap.add_argument("--rounds", type=int, default=1)
-    ap.add_argument("--timeout", type=float, default=300.0, help="seconds per child")
-    ap.add_argument("--log", help="also write the report here")
-    args = ap.parse_args()
-    libs = {"OLD": os.path.abspath(args.old), "NEW": os.path.abspath(args.new)}
-    lines = []
-
-    def say(text=""):
-        print(text, flush=True)
-        lines.append(text)
-
-    def finish(rc):
-        if args.log:
-            with open(args.log, "w") as f:
-                f.write("\n".join(lines) + "\n")
-        sys.exit(rc)
-
-    for tag, path in libs.items():
-        if not os.path.exists(path):
-            sys.exit(f"{tag}: {path} does not exist")
-        say(f"{tag} = {path}")
-    medians, differ = {"OLD": {}, "NEW": {}}, 0
-    with tempfile.TemporaryDirectory() as tmp:
-        for rnd in range(args.rounds):
-            got = {}
-            for tag, path in libs.items():
-                out = os.path.join(tmp, f"{tag}_{rnd}")
-                os.makedirs(out)
-                say(f"round {rnd + 1}, {tag}:")
-                try:
-                    rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out],
-                                        env=dict(os.environ, SWIMMER_HIP_LIB=path), timeout=args.timeout).returncode
-                except subprocess.TimeoutExpired:
-                    rc = 124
-                if rc != 0:
-                    say(f"{tag} child ended with status {rc}: stopping here")
-                    finish(rc if rc > 0 else 128 - rc)
-                with open(os.path.join(out, "times.json")) as f:
-                    got[tag] = (dict(np.load(os.path.join(out, "cases.npz"))), json.load(f))
-            (a_old, t_old), (a_new, t_new) = got["OLD"], got["NEW"]
-            bad = [k for k in a_old if k not in a_new or not np.array_equal(a_old[k], a_new[k],
-                                                                            equal_nan=a_old[k].dtype.kind == "f")]
-            bad += [k for k in a_new if k not in a_old]
-            differ += len(bad)
-            say(f"round {rnd + 1}: {len(a_old) - len(bad)} of {len(a_old)} arrays bit-equal"
-                + ("" if not bad else "; DIFFERENT: " + ", ".join(bad)))
-            for key in t_old:
-                o, n = t_old[key], t_new[key]
-                medians["OLD"].setdefault(key, []).append(statistics.median(o))
-                medians["NEW"].setdefault(key, []).append(statistics.median(n))
-                say(f"  {key:<42} ms  OLD median {statistics.median(o):8.4f} ({min(o):.4f} .. {max(o):.4f})   "
-                    f"NEW median {statistics.median(n):8.4f} ({min(n):.4f} .. {max(n):.4f})   "
-                    f"NEW / OLD {statistics.median(n) / statistics.median(o):.4f}")
-    above = 0
-    if args.rounds > 1:
-        say("over the rounds (ms): OLD's medians min .. max are the noise floor; NEW's medians must not exceed "
-            "OLD's max")
-        for key, o in medians["OLD"].items():
-            n = medians["NEW"][key]
-            ok = max(n) <= max(o)
-            above += 0 if ok else 1
-            say(f"  {key:<42} OLD {min(o):8.4f} .. {max(o):8.4f}   NEW {min(n):8.4f} .. {max(n):8.4f}   "
-                + ("at or below" if ok else "ABOVE"))
-    say("arrays: " + ("all bit-equal" if not differ else f"{differ} DIFFERENT"))
-    finish(1 if differ else 3 if above else 0)
-
-
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "--child":
         child(sys.argv[2])
     else:
-        main()
+        ab_common.compare(__doc__.split("\n")[0], __file__)
