@@ -4,15 +4,26 @@ tests compare with these launches, so a wrong instantiation here is one they wou
 only, no GPU: tests/test_rollout_matrix_cpu.py checks on the oracle alone that the cases exercise what
 tests/test_rollout_matrix_gpu.py compares.
 
-INSTANTIATIONS lists the 74 kernels (the twin model, rollout_kernel<N, ARS, true>, stays with tests/test_twin.py)
-with the launch that reaches each: entry point, flags, environment, and whether traj / moments are passed (the dispatch
-rules: plan_rollouts, launch_oct3, launch_quad3, launch_row, launch_lane).
+INSTANTIATIONS lists the 88 kernels, the twin model's rollout_kernel<N, ARS, true> included, with the launch that
+reaches each: entry point, flags, environment, and whether traj / moments are passed (the dispatch rules:
+plan_rollouts, launch_oct3, launch_quad3, launch_row, launch_lane).
 
 The reference is oracle.swimmer_oracle on the "realworld" parameters with direction (0.6, -0.8): a swapped Gdot
 component shows in every trajectory, and in the returns of the launches with start states (from rest and over these
 horizons the returns themselves are ~ 1e-8).  ARS policies are built here in NumPy, P + nu delta_i for rollout 2i and P - nu delta_i
 for rollout 2i + 1 with i counted from dir_begin; the deltas array has rows before and behind the slice that a launch
 uses, filled with values that would show in every trajectory if read.
+
+THE TWIN MODEL (FLAG_MODEL_TWIN, csrc/swimmer_twin.h: the reference's native RL-Glue swimmer) is the form "twin": it
+always runs in the lane form, so its shapes are the lane form's, all of them.  Its reference steps oracle.twin_step
+(oracle/twin_oracle.c, pinned entry by entry to the reference's recorded system in tests/test_twin.py) from Python:
+per step u = (P diag(inv_std)) (s - mean), the return the sum of the rewards, the start 0.001 in every entry where
+there is no state0.  Parameters: the second of step_matrix_cases.TWIN_SETS, (0.8, 1.2, 10.2) with h = 0.003 and the
+same direction (0.6, -0.8).  From the 0.001 start the returns are ~ 1e-3, not a rounding residue: a swapped Gdot
+component shows in the returns of the ARS launches as well.  The step itself is pinned at every n by
+tests/test_step_matrix_gpu.py; what these cases add is everything the lane body wraps around it -- the P +- nu delta
+prologue, the whitening fold and its bias, the start, the stores, the moment butterfly (which centres the angle
+columns on pi/2 for both models: moment_rows is the same).
 
 SHAPES.  The smallest that still reach each mechanism:
  * horizons HORIZONS at 21 rollouts (ARS: 11 directions = 22): row and quad trips are 4 steps, the mirror-quad trip 8
@@ -47,8 +58,13 @@ from conftest import PARAM_SETS
 from oracle import swimmer_oracle as oracle
 from swimmer_amd import _lib
 
+import step_matrix_cases
+
 L_I, M_I, K, H_STEP = PARAM_SETS["realworld"]
 DIRECTION = (0.6, -0.8)
+TWIN_PARAMS = step_matrix_cases.TWIN_SETS[1]       # (l_i, m_i, k, h, direction) of the twin cases
+TWIN_START = 0.001            # kTwinStart: every entry of the twin's start state (env_start)
+TWIN_FLAGS = _lib.FLAG_MODEL_TWIN | _lib.FLAG_ROLLOUT_LANE
 TOL = 1e-9                    # relative to max(1, |ref|): the project's bound for runs of up to 1000 steps (TRAJ_TOL)
 STABLE = 1e-10                # what inputs scaled by 1 + 1e-13 may move the oracle's own trajectory
 MOM_GROUP = 16                # rollouts per V2 moment row (kMomGroup)
@@ -84,21 +100,23 @@ def _instantiations():
         for ars in (0, 1):
             out.append(Inst(f"rollout_kernelILi{n}ELb{ars}ELb0E", "lane", n, b(ars), None, None,
                             _lib.FLAG_ROLLOUT_LANE, None))
+            out.append(Inst(f"rollout_kernelILi{n}ELb{ars}ELb1E", "twin", n, b(ars), None, None, TWIN_FLAGS, None))
     return tuple(out)
 
 
 INSTANTIATIONS = _instantiations()
 KERNEL_NAMES = ("rollout_row_kernel", "rollout_oct3_kernel", "rollout_octp3_kernel", "rollout_octl3_kernel",
                 "rollout_quad3_kernel", "rollout_kernelILi")
-TWIN_SYMBOL = r"rollout_kernelILi\dELb[01]ELb1E"
 
 # the cases of the GPU test: (form, n).  The n = 3 cases run on the quad kernel in a child process.
-FORMS = (("oct3", 3),) + tuple(("row", n) for n in range(4, 9)) + tuple(("lane", n) for n in range(2, 9))
+FORMS = (("oct3", 3),) + tuple(("row", n) for n in range(4, 9)) + tuple(("lane", n) for n in range(2, 9)) + \
+    tuple(("twin", n) for n in range(2, 9))
+LANE_FORMS = ("lane", "twin")                      # one rollout per lane of a 64-lane workgroup
 
 
 def variants(form):
     """The launches of one shape: (name, traj, moments, flags) -- every (TRAJ, MOM) combination the form has."""
-    flags = _lib.FLAG_ROLLOUT_LANE if form == "lane" else 0
+    flags = {"lane": _lib.FLAG_ROLLOUT_LANE, "twin": TWIN_FLAGS}.get(form, 0)
     out = [("none", False, False, flags), ("traj", True, False, flags), ("mom", False, True, flags),
            ("traj_mom", True, True, flags)]
     if form == "oct3":          # capture + moments: the lean packed kernel (default), the first packed one, the split one
@@ -136,7 +154,7 @@ POISON = 1e3                  # scale of the rows of deltas that no launch may r
 def plain_shapes(form):
     """(H, R, with_state0) of the sw_rollout_f64 launches of a case."""
     sizes = [(H, R_AT_HORIZONS) for H in HORIZONS] + [(H_AT_BATCHES, R) for R in BATCHES]
-    if form == "lane":
+    if form in LANE_FORMS:
         sizes += [(H_AT_BATCHES, R) for R in LANE_BATCHES]
     return tuple((H, R, s0) for H, R in sizes for s0 in (True, False))
 
@@ -145,7 +163,7 @@ def ars_shapes(form):
     """(H, n_dir, dir_begin) of the sw_ars_rollouts_f64 launches of a case."""
     out = [(H, DIRS_AT_HORIZONS, DIR_BEGINS[1]) for H in HORIZONS]
     out += [(H_AT_BATCHES, nd, db) for nd in N_DIRS for db in DIR_BEGINS]
-    if form == "lane":
+    if form in LANE_FORMS:
         out += [(H_AT_BATCHES, nd, DIR_BEGINS[1]) for nd in LANE_N_DIRS]
     return tuple(out)
 
@@ -154,11 +172,22 @@ def _rs(*key):
     return np.random.RandomState(zlib.crc32(repr(key).encode()))
 
 
-def oracle_params(n):
-    return oracle.OracleParams.make(n, L_I, M_I, K, H_STEP, DIRECTION)
+def model_of(form):
+    return "twin" if form == "twin" else "gym"
 
 
-def reset_state(n):
+def model_params(model="gym"):
+    """(l_i, m_i, k, h, direction) of a model's cases."""
+    return TWIN_PARAMS if model == "twin" else (L_I, M_I, K, H_STEP, DIRECTION)
+
+
+def oracle_params(n, model="gym"):
+    return oracle.OracleParams.make(n, *model_params(model))
+
+
+def reset_state(n, model="gym"):
+    if model == "twin":
+        return np.full(2 * n + 2, TWIN_START)
     s = np.zeros(2 * n + 2)
     s[2::2] = np.pi / 2
     return s
@@ -180,14 +209,18 @@ def start_states(rs, R, n):
     return st
 
 
-def plain_inputs(n, H, R, with_state0, v2):
-    """dict(n, H, policies [R, m, d], state0 [R, d] or None, mean, var [d] or None)."""
+def _model_key(model):
+    return () if model == "gym" else (model,)          # the Gym cases keep the streams their records were made with
+
+
+def plain_inputs(n, H, R, with_state0, v2, model="gym"):
+    """dict(n, H, model, policies [R, m, d], state0 [R, d] or None, mean, var [d] or None)."""
     d, m = 2 * n + 2, n - 1
-    rs = _rs("plain", n, H, R, with_state0, v2)
+    rs = _rs("plain", n, H, R, with_state0, v2, *_model_key(model))
     policies = 0.3 * rs.uniform(-1, 1, (R, m, d))
     mean, var = _whitening(rs, d, v2)
-    return dict(n=n, H=H, policies=policies, state0=start_states(rs, R, n) if with_state0 else None, mean=mean,
-                var=var)
+    return dict(n=n, H=H, model=model, policies=policies, state0=start_states(rs, R, n) if with_state0 else None,
+                mean=mean, var=var)
 
 
 def ars_policies(policy, deltas, nu, dir_begin, n_dir):
@@ -196,31 +229,51 @@ def ars_policies(policy, deltas, nu, dir_begin, n_dir):
     return np.stack([policy + step, policy - step], axis=1).reshape((2 * n_dir,) + policy.shape)
 
 
-def ars_inputs(n, H, n_dir, dir_begin, v2):
-    """dict(n, H, policy [m, d], deltas [dir_begin + 2 n_dir + EXTRA_ROWS, m, d], nu, dir_begin, n_dir, policies, state0 =
-    None, mean, var)."""
+def ars_inputs(n, H, n_dir, dir_begin, v2, model="gym"):
+    """dict(n, H, model, policy [m, d], deltas [dir_begin + 2 n_dir + EXTRA_ROWS, m, d], nu, dir_begin, n_dir, policies,
+    state0 = None, mean, var)."""
     d, m = 2 * n + 2, n - 1
-    rs = _rs("ars", n, H, n_dir, dir_begin, v2)
+    rs = _rs("ars", n, H, n_dir, dir_begin, v2, *_model_key(model))
     policy = 0.2 * rs.uniform(-1, 1, (m, d))
     deltas = POISON * (1 + rs.rand(dir_begin + 2 * n_dir + EXTRA_ROWS, m, d))
     deltas[dir_begin:dir_begin + n_dir] = rs.standard_normal((n_dir, m, d))
     mean, var = _whitening(rs, d, v2)
-    return dict(n=n, H=H, policy=policy, deltas=deltas, nu=NU, dir_begin=dir_begin, n_dir=n_dir,
+    return dict(n=n, H=H, model=model, policy=policy, deltas=deltas, nu=NU, dir_begin=dir_begin, n_dir=n_dir,
                 policies=ars_policies(policy, deltas, NU, dir_begin, n_dir), state0=None, mean=mean, var=var)
+
+
+def twin_step(p, state, u):
+    """One step of the twin oracle: (next state, reward)."""
+    return oracle.twin_step(p, state, u)
+
+
+def twin_rollout(p, H, policy, mean, var, start):
+    """H steps of the twin oracle under a linear policy: u = (P diag(var ** -0.5)) (s - mean), plain P s without
+    whitening; (the sum of the rewards, traj [H, d])."""
+    W = policy if mean is None else policy * var ** -0.5
+    s, total, traj = np.array(start, dtype=np.float64), 0.0, np.empty((H, start.shape[0]))
+    for t in range(H):
+        s, rew = twin_step(p, s, W @ (s if mean is None else s - mean))
+        total += rew
+        traj[t] = s
+    return total, traj
 
 
 def reference(inp, scale=1.0):
     """The oracle on a launch's rollouts: dict(returns [R], traj [R, H, d], final [R, d], start [R, d]).  scale: a
     factor on the policies and the start states (the conditioning check of the CPU test)."""
-    n, H = inp["n"], inp["H"]
-    p = oracle_params(n)
+    n, H, model = inp["n"], inp["H"], inp.get("model", "gym")
+    p = oracle_params(n, model)
     policies = inp["policies"] * scale
     R = policies.shape[0]
-    start = np.tile(reset_state(n), (R, 1)) if inp["state0"] is None else inp["state0"] * scale
+    start = np.tile(reset_state(n, model), (R, 1)) if inp["state0"] is None else inp["state0"] * scale
     rets, traj = np.empty(R), np.empty((R, H, 2 * n + 2))
     for r in range(R):
-        rets[r], traj[r] = oracle.rollout(p, H, policies[r], inp["mean"], inp["var"],
-                                          None if inp["state0"] is None else start[r])
+        if model == "twin":
+            rets[r], traj[r] = twin_rollout(p, H, policies[r], inp["mean"], inp["var"], start[r])
+        else:
+            rets[r], traj[r] = oracle.rollout(p, H, policies[r], inp["mean"], inp["var"],
+                                              None if inp["state0"] is None else start[r])
     return dict(returns=rets, traj=traj, final=traj[:, -1] if H else start, start=start)
 
 

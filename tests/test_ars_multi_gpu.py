@@ -17,6 +17,9 @@ if ROOT not in sys.path:      # the quad-form child below runs this file as a sc
 import swimmer_amd as sw  # noqa: E402
 from swimmer_amd import kernels  # noqa: E402
 
+from batch_kernel_cases import (MORE_INSTANTIATIONS, MORE_S, MULTI_AGENTS, MULTI_DIRS, MULTI_FORMS,  # noqa: E402
+                                MULTI_NS, more_id)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -67,10 +70,10 @@ def _compare_rollouts(p, n, N, S, v2, with_moments=True):
 
 
 @pytest.mark.parametrize("v2", [False, True], ids=["V1", "V2"])
-@pytest.mark.parametrize("form", ["auto", "lane"])
-@pytest.mark.parametrize("S", [1, 3, 9])
-@pytest.mark.parametrize("N", [1, 7, 8, 9])      # 2N = 2, 14, 16, 18: below, just below, exactly, across a moment row
-@pytest.mark.parametrize("n", [2, 3, 6])         # lane only, mirror-quad, row
+@pytest.mark.parametrize("form", MULTI_FORMS)
+@pytest.mark.parametrize("S", MULTI_AGENTS)
+@pytest.mark.parametrize("N", MULTI_DIRS)        # 2N = 2, 14, 16, 18: below, just below, exactly, across a moment row
+@pytest.mark.parametrize("n", MULTI_NS)          # lane only, mirror-quad, row
 def test_multi_rollouts_equal_single_agent_launches(n, N, S, form, v2):
     # auto: S * 16 * ceil(2N / 16) <= 288 slots, far below 8192 -- the batch and the single launches take the same form
     p = sw.SwParams.make(n, 0.8, 1.2, 10.2, 1e-3, flags=sw._lib.kernel_flags(form))
@@ -84,37 +87,17 @@ def test_multi_rollouts_equal_single_agent_launches(n, N, S, form, v2):
 #    MOM = false too, which the product leaves out.  MOM follows the moments pointer alone: one V2 launch without
 #    moments (whitening, MOM = false) at n = 5.
 #  * ars_multi_lane_kernel<N, false> at the same n.
-#  * ars_multi_lane_kernel<N, true>: the twin model (its single-agent rollouts are checked against the C oracle in
-#    tests/test_twin.py; equality with them is the reference here).
+#  * ars_multi_lane_kernel<N, true>, every n = 2..8: the twin model (its single-agent rollouts are held to the twin
+#    oracle at every n in tests/test_rollout_matrix_gpu.py, the twin cases; equality with them is the reference here).
 # The n = 3 forms without moments: test_multi_rollouts_without_moments_and_status (mirror-quad) and the quad child.
-MORE_INSTANTIATIONS = [
-    ("auto", False, 4, 7, False, False), ("auto", False, 4, 7, True, True),
-    ("auto", False, 4, 9, False, False), ("auto", False, 4, 9, True, True),
-    ("auto", False, 5, 7, False, False), ("auto", False, 5, 7, True, True),
-    ("auto", False, 5, 9, False, False), ("auto", False, 5, 9, True, True), ("auto", False, 5, 9, True, False),
-    ("auto", False, 6, 7, False, False), ("auto", False, 6, 9, False, False),
-    ("auto", False, 7, 7, False, False), ("auto", False, 7, 7, True, True),
-    ("auto", False, 7, 9, False, False), ("auto", False, 7, 9, True, True),
-    ("auto", False, 8, 7, False, False), ("auto", False, 8, 7, True, True),
-    ("auto", False, 8, 9, False, False), ("auto", False, 8, 9, True, True),
-    ("lane", False, 4, 9, False, True), ("lane", False, 4, 9, True, True),
-    ("lane", False, 5, 9, False, True), ("lane", False, 5, 9, True, True),
-    ("lane", False, 7, 9, False, True), ("lane", False, 7, 9, True, True),
-    ("lane", False, 8, 9, False, True), ("lane", False, 8, 9, True, True),
-    ("lane", True, 2, 9, False, True), ("lane", True, 2, 9, True, True),
-    ("lane", True, 3, 9, False, True), ("lane", True, 3, 9, True, True),
-    ("lane", True, 6, 9, False, True), ("lane", True, 6, 9, True, True),
-    ("lane", True, 8, 9, False, True), ("lane", True, 8, 9, True, True),
-]
-
-
+# The list itself is MORE_INSTANTIATIONS of tests/batch_kernel_cases.py, where tests/test_batch_kernels_cpu.py derives
+# from it which kernels are launched.
 @pytest.mark.parametrize("form,twin,n,N,v2,with_moments", MORE_INSTANTIATIONS,
-                         ids=[f"{f}-{'twin' if t else 'swimmer'}-n{n}-N{N}-{'V2' if v else 'V1'}-{'mom' if w else 'nomom'}"
-                              for f, t, n, N, v, w in MORE_INSTANTIATIONS])
+                         ids=[more_id(*case) for case in MORE_INSTANTIATIONS])
 def test_multi_rollouts_at_every_compiled_n_and_model(form, twin, n, N, v2, with_moments):
     flags = sw._lib.kernel_flags(form) | (sw._lib.FLAG_MODEL_TWIN if twin else 0)
     p = sw.SwParams.make(n, 0.8, 1.2, 10.2, 1e-3, flags=flags)
-    _compare_rollouts(p, n, N, 3, v2, with_moments)
+    _compare_rollouts(p, n, N, MORE_S, v2, with_moments)
 
 
 def test_multi_rollouts_without_moments_and_status():

@@ -17,11 +17,13 @@ if ROOT not in sys.path:      # the quad-form child below runs this file as a sc
 
 import swimmer_amd as sw  # noqa: E402
 from swimmer_amd import kernels  # noqa: E402
-from swimmer_amd._lib import FLAG_MODEL_TWIN, FLAG_ROLLOUT_LANE, STATUS_PARAM, SwParams, kernel_flags  # noqa: E402
+from swimmer_amd._lib import STATUS_PARAM, SwParams  # noqa: E402
 from swimmer_amd.ars import ars_agent, safe_exploration  # noqa: E402
 from swimmer_amd.ars.ensemble import fold_reference, sphere_ensemble  # noqa: E402
 from swimmer_amd.ars.ensemble_kernels import ars_gate_ensemble  # noqa: E402
 from swimmer_amd.ars.parameters import Threshold  # noqa: E402
+
+from batch_kernel_cases import ENSEMBLE_FORMS as FORMS, flags_of as _flags  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -43,10 +45,6 @@ def _np(t):
 
 def _row(t, a):
     return None if t is None else t[a]
-
-
-def _flags(form):
-    return FLAG_MODEL_TWIN | FLAG_ROLLOUT_LANE if form == "twin" else kernel_flags(form)
 
 
 def _inputs(n, N, S, v2):
@@ -163,15 +161,11 @@ def _check_form(n, form, N=9):
         _check_one_member_equals_the_multi_gate(n, form, v2, N=N)
 
 
-FORMS = [(3, "auto", 9), (4, "auto", 9), (5, "auto", 9), (6, "auto", 9), (7, "auto", 9), (8, "auto", 9),
-         (2, "auto", 9), (3, "lane", 9), (5, "lane", 9), (3, "twin", 9), (2, "auto", 33), (3, "lane", 33),
-         (5, "lane", 33), (3, "twin", 33)]
-
-
 @pytest.mark.parametrize("n,form,N", FORMS, ids=[f"n{n}-{form}-N{N}" for n, form, N in FORMS])
 def test_members_equal_the_single_gate_and_the_fold_its_restatement(n, form, N):
-    """n = 3 auto: mirror-quad; n = 4..8 auto: row; n = 2 and 'lane' / 'twin': one rollout per lane (N = 33: 66
-    rollouts cross its 64-slot workgroup); 2N = 18 crosses the 16-slot group of the other forms."""
+    """ENSEMBLE_FORMS (tests/batch_kernel_cases.py).  n = 3 auto: mirror-quad; n = 4..8 auto: row; n = 2 and 'lane' /
+    'twin': one rollout per lane, every n = 2..8 in both models (N = 33: 66 rollouts cross its 64-slot workgroup);
+    2N = 18 crosses the 16-slot group of the other forms."""
     _check_form(n, form, N)
 
 

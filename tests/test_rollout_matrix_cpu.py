@@ -3,15 +3,16 @@ library holds, that its loop-crossing cases cross the loops, and that its refere
 
  * COVERAGE.  The kernel symbols of the built library whose names are rollout_row_kernel, rollout_oct3_kernel,
    rollout_octp3_kernel, rollout_octl3_kernel, rollout_quad3_kernel or rollout_kernel<N, ..> (the names alone: the
-   safe-exploration kernels safe_rollout_* contain them and are other kernels), the twin model's left to
-   tests/test_twin.py: each is named by exactly one entry of INSTANTIATIONS, and each entry exists.  A template
-   argument added later fails here until it has a case; every entry is reached by a launch of the GPU test.
+   safe-exploration kernels safe_rollout_* contain them and are other kernels), the twin model's included: each is
+   named by exactly one entry of INSTANTIATIONS, and each entry exists.  A template argument added later fails here
+   until it has a case; every entry is reached by a launch of the GPU test.
  * CROSSINGS.  On the oracle's trajectories the restated loop control shows, for each n = 4..8, a wave that goes
    unchecked -> checked, one that goes checked -> unchecked, and a wave in the checked loop while three of its rollouts
    are below 10 rad/s; both kinds of crossing happen at steps that are no multiple of four; no evaluated test comes
    closer than 1e-5 rad to its threshold of 0.04 rad (a kernel within 1e-9 of the oracle takes the oracle's loops).
  * REFERENCES.  Every oracle trajectory is finite, and inputs scaled by 1 + 1e-13 move the oracle's own trajectory
-   by at most 1e-10: a tenth of the bound the GPU test holds the kernels to.
+   by at most 1e-10: a tenth of the bound the GPU test holds the kernels to.  The twin cases too (first run: at
+   most 4.7e-12 at any n).
 """
 import os
 import re
@@ -41,10 +42,14 @@ def _launched():
     return out
 
 
-def test_the_list_has_74_entries_and_the_gpu_test_launches_each():
-    assert len(mc.INSTANTIATIONS) == 74 and len({i.symbol for i in mc.INSTANTIATIONS}) == 74
+def test_the_list_has_88_entries_and_the_gpu_test_launches_each():
+    assert len(mc.INSTANTIATIONS) == 88 and len({i.symbol for i in mc.INSTANTIATIONS}) == 88
     assert _launched() == set(mc.INSTANTIATIONS)
-    assert [sum(i.symbol.startswith(k) for i in mc.INSTANTIATIONS) for k in mc.KERNEL_NAMES] == [40, 8, 2, 2, 8, 14]
+    assert [sum(i.symbol.startswith(k) for i in mc.INSTANTIATIONS) for k in mc.KERNEL_NAMES] == [40, 8, 2, 2, 8, 28]
+    assert sum(i.symbol.endswith("ELb1E") and i.form == "twin" for i in mc.INSTANTIATIONS) == 14
+    # the twin model runs the lane form's shapes, all of them
+    assert mc.plain_shapes("twin") == mc.plain_shapes("lane") and mc.ars_shapes("twin") == mc.ars_shapes("lane")
+    assert [v[:3] for v in mc.variants("twin")] == [v[:3] for v in mc.variants("lane")]
 
 
 @needs_tools
@@ -54,8 +59,7 @@ def test_every_compiled_instantiation_is_listed_once():
     pattern = re.compile("(?:" + "|".join(f"{len(k)}{k}I" for k in names) + ")")
     symbols = sorted({l.split("<", 1)[1][:-2] for l in _disassemble()
                       if l.startswith("0000") and l.endswith(">:") and pattern.search(l)})
-    symbols = [s for s in symbols if not re.search(mc.TWIN_SYMBOL, s)]
-    assert len(symbols) == 74, (len(symbols), symbols)
+    assert len(symbols) == 88, (len(symbols), symbols)
     for s in symbols:
         named_by = [i.symbol for i in mc.INSTANTIATIONS if i.symbol + "E" in s]
         assert len(named_by) == 1, (s, named_by)
@@ -102,11 +106,12 @@ def test_the_crossing_cases_cross_the_loops(n):
 
 
 def _launches(form, n):
+    model = mc.model_of(form)
     for v2 in (False, True):
         for H, R, s0 in mc.plain_shapes(form):
-            yield mc.plain_inputs(n, H, R, s0, v2)
+            yield mc.plain_inputs(n, H, R, s0, v2, model)
         for H, n_dir, dir_begin in mc.ars_shapes(form):
-            yield mc.ars_inputs(n, H, n_dir, dir_begin, v2)
+            yield mc.ars_inputs(n, H, n_dir, dir_begin, v2, model)
     if n in mc.CROSSING and form == "row":
         yield mc.crossing_case(n)
         yield mc.crossing_case(n, from_rest=True)

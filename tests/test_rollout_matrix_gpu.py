@@ -1,5 +1,6 @@
-"""Every compiled instantiation of the single-agent rollout kernels (sw_rollout_f64, sw_ars_rollouts_f64: the 74 of
-tests/rollout_matrix_cases.py INSTANTIATIONS) against oracle.swimmer_oracle.  This file is the ROOT of the suite's
+"""Every compiled instantiation of the single-agent rollout kernels (sw_rollout_f64, sw_ars_rollouts_f64: the 88 of
+tests/rollout_matrix_cases.py INSTANTIATIONS) against oracle.swimmer_oracle -- the twin model's 14,
+rollout_kernel<N, ARS, true>, against oracle.twin_step stepped from Python.  This file is the ROOT of the suite's
 tree of bit-equalities: the multi-agent, gate, counted and safe-batch tests compare their kernels with these launches,
 so a wrong instantiation here is one they would agree with.  tests/test_rollout_matrix_cpu.py checks that the list is
 what the library holds and that the cases exercise what is compared here.
@@ -31,6 +32,14 @@ neither, through the plain entry point with their start states and through the A
 The worst figures of every case go to observed("rollout_matrix", ...), the child's to "rollout_matrix_quad";
 profiles/rollout_matrix_observed.json and rollout_matrix_quad_observed.json hold those of the first run (7008 + 708
 launches: trajectory <= 1.5e-14, returns <= 2.8e-14, moment rows <= 1.3e-13, no pair with different bits).
+
+THE TWIN CASES (form "twin", n = 2..8: rollout_kernel<N, ARS, true>, the lane form's shapes and variants, all of
+them) are the root for everything that is compared bit for bit with twin launches: ars_multi_lane_kernel<N, true> in
+tests/test_ars_multi_gpu.py and the twin forms of the gate, counted and ensemble tests.  Same checks, same bound.  From
+the twin's 0.001 start the returns are ~ 1e-3, not a residue, and every moment entry has terms of its own: the per-entry
+figure is small here too.  profiles/rollout_matrix_twin_observed.json holds the twin cases' figures of their first run
+(3920 launches: trajectory <= 6.9e-15, returns <= 1.2e-15, final_state <= 3.6e-15, moment rows <= 6.1e-16, moment
+entries <= 1.7e-13, no pair with different bits).
 """
 import ctypes
 import os
@@ -86,7 +95,7 @@ def launch(sw, inp, on_dev, ars, want_traj, want_mom, flags):
     n, H = inp["n"], inp["H"]
     d, R = 2 * n + 2, inp["policies"].shape[0]
     B = (R + mc.MOM_GROUP - 1) // mc.MOM_GROUP
-    p = sw.SwParams.make(n, mc.L_I, mc.M_I, mc.K, mc.H_STEP, mc.DIRECTION, flags=flags)
+    p = sw.SwParams.make(n, *mc.model_params(inp.get("model", "gym")), flags=flags)
     ret, status = filled(R + GUARD), filled(R + GUARD, -1, torch.int32)
     traj = filled((H + 1) * d * R) if want_traj else None
     mom = filled((B + 1) * 2 * d) if want_mom else None
@@ -213,14 +222,15 @@ def finish(F, name):
 @pytest.mark.parametrize("entry", ("plain", "ars"))
 @pytest.mark.parametrize("form,n", mc.FORMS)
 def test_every_instantiation_against_the_oracle(sw, form, n, entry):
-    F = Figures()
+    F, model = Figures(), mc.model_of(form)
     for v2 in (False, True):
         if entry == "plain":
             for H, R, s0 in mc.plain_shapes(form):
-                run_shape(sw, F, form, mc.plain_inputs(n, H, R, s0, v2), ("H", H, "R", R, "state0", s0, "v2", v2))
+                run_shape(sw, F, form, mc.plain_inputs(n, H, R, s0, v2, model),
+                          ("H", H, "R", R, "state0", s0, "v2", v2))
         else:
             for H, n_dir, dir_begin in mc.ars_shapes(form):
-                run_shape(sw, F, form, mc.ars_inputs(n, H, n_dir, dir_begin, v2),
+                run_shape(sw, F, form, mc.ars_inputs(n, H, n_dir, dir_begin, v2, model),
                           ("H", H, "n_dir", n_dir, "dir_begin", dir_begin, "v2", v2))
     finish(F, f"{form}_n{n}_{entry}")
 

@@ -10,11 +10,12 @@ import torch
 
 import swimmer_amd as sw
 from swimmer_amd import kernels
-from swimmer_amd._lib import SwParams, kernel_flags
+from swimmer_amd._lib import SwParams
 from swimmer_amd.ars.parameters import Threshold
 from conftest import GOLDEN
 from safe_agent_oracle import SafeArsOracle
 from test_safe_ars_agent_cpu import DB, _close, _fixture, _params
+from batch_kernel_cases import GATE_SHAPES, flags_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -79,14 +80,12 @@ def _host_rule(r, thr):
     return (~(r[:, 0] <= thr) & ~(r[:, 1] <= thr)).astype(np.int32)
 
 
-GATE_SHAPES = [(n, N, form) for n in range(2, 9) for N in (1, 7, 64, 2049) for form in ("auto", "lane")] + \
-              [(3, N, "quad") for N in (1, 7, 64, 2049)] + [(3, 4097, "auto"), (6, 4097, "auto")]
-
-
 @pytest.mark.parametrize("n,N,form", GATE_SHAPES)
 def test_gate_kernel_against_ars_rollouts(n, N, form):
+    """GATE_SHAPES (tests/batch_kernel_cases.py): every ars_gate_* kernel, the twin model's lane ones ("twin": its
+    ars_rollouts are held to the oracle in tests/test_rollout_matrix_gpu.py) included."""
     H = 60
-    p = SwParams.make(n, 0.9, 1.1, 9.5, 1e-3, (1.0, 0.0), flags=kernel_flags(form))
+    p = SwParams.make(n, 0.9, 1.1, 9.5, 1e-3, (1.0, 0.0), flags=flags_of(form))
     policy, deltas, mean, inv_std = _gate_inputs(n, N, 1000 * n + N, v2=(N % 2 == 1))
     nu = 0.05
     ref = kernels.ars_rollouts(p, H, policy, deltas, nu, 0, N, mean=mean, inv_std=inv_std)

@@ -16,9 +16,11 @@ if ROOT not in sys.path:      # the quad-form child below runs this file as a sc
 
 import swimmer_amd as sw  # noqa: E402
 from swimmer_amd import kernels  # noqa: E402
-from swimmer_amd._lib import SwParams, kernel_flags  # noqa: E402
+from swimmer_amd._lib import SwParams  # noqa: E402
 from swimmer_amd.ars import ars_agent, safe_exploration  # noqa: E402
 from swimmer_amd.ars.parameters import Threshold  # noqa: E402
+
+from batch_kernel_cases import SAFE_BATCH_FORMS, flags_of as _flags  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +54,7 @@ def _np(t):
 
 def _check_gate(n, form, v2, S=3, N=9, H=40):
     """ars_gate_multi against one ars_gate call per agent in the agent's own simulator."""
-    flags = kernel_flags(form)
+    flags = _flags(form)
     base = SwParams.make(n, *REAL, 1e-3, (1.0, 0.0), flags=flags)
     policy, deltas, mean, inv_std = _inputs(n, N, S, v2)
     p_sim = [SwParams.make(n, *SIMS[a], 1e-3, (1.0, 0.0), flags=flags) for a in range(S)]
@@ -95,12 +97,20 @@ PATTERNS = [  # per round, per agent: hand-made admit flags over N = 9 direction
 def _check_counted(n, form, v2, S=3, N=9, H=40):
     """ars_pack_admitted, ars_rollouts_multi_counted and ars_update_multi_counted on hand-made flags against
     ars_rollouts / ars_update with n_dir = k on the packed deltas."""
-    p = SwParams.make(n, *REAL, 1e-3, (1.0, 0.0), flags=kernel_flags(form))
+    p = SwParams.make(n, *REAL, 1e-3, (1.0, 0.0), flags=_flags(form))
     m, d = p.m, p.d
     policy0, deltas, mean0, inv_std0 = _inputs(n, N, S, v2)
     rows = kernels.moments_blocks(2 * N)
     assert rows == 2
-    state = dict(policy=policy0.clone(), running=torch.zeros((S, 1 + 2 * d), **F64) if v2 else None,
+    running0 = torch.zeros((S, 1 + 2 * d), **F64) if v2 else None
+    if v2 and form == "twin":
+        # The twin barely moves in 40 steps from its 0.001 start (Gdot x: a spread of 5e-7), and statistics made of
+        # such a round alone whiten the next one into a feedback gain of 2e6: the simulator itself diverges to NaN
+        # within 30 steps (on the CPU oracle too), and NaN returns compare unequal.  So the twin's agents start, as
+        # an agent does after an iteration, from running statistics that already hold 2 N H states of unit variance.
+        running0[:, 0] = 2 * N * H
+        running0[:, 1 + d:] = 2 * N * H
+    state = dict(policy=policy0.clone(), running=running0,
                  mean=mean0, inv_std=inv_std0, sigma=torch.zeros(S, **F64))
     alpha, b = 0.02, float(N)
     seen = set()
@@ -184,9 +194,10 @@ def _check_form(n, form):
         _check_counted(n, form, v2)
 
 
-@pytest.mark.parametrize("n,form", [(3, "auto"), (6, "auto"), (2, "auto"), (3, "lane")],
-                         ids=["mirror-quad", "row", "lane-n2", "lane-n3"])
+@pytest.mark.parametrize("n,form", [c[:2] for c in SAFE_BATCH_FORMS], ids=[c[2] for c in SAFE_BATCH_FORMS])
 def test_kernels_equal_their_single_agent_twins(n, form):
+    """SAFE_BATCH_FORMS (tests/batch_kernel_cases.py): mirror-quad, the row form at every n = 4..8, the lane form at
+    every n = 2..8 in both models ("twin": the agents' (l_i, m_i, k) are the twin's constants as they are)."""
     _check_form(n, form)
 
 

@@ -86,7 +86,7 @@ def random_states(rng, n, B):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [2, 3, 4, 5, 6, 8])
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 6, 7, 8])
 def test_hip_twin_model_vs_oracle(n):
     import torch
     import swimmer_amd as sw
