@@ -53,6 +53,8 @@
  *                        reference does not have)   cacla/cacla_safe_agent.py:161-188, safe_ars/ars.py:111-122
  *   sw_lqr_cacla_run_f64 CACLA_LQR_agent.run and the safe agents' run loops on the LQR environments, one agent per
  *                        lane   cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py, envs/gym_lqr/lqr_env.py
+ *   sw_rlglue_ars_run_f64  SwimmerARSAgent under SwimmerExperiment's loop on the native swimmer, one agent per
+ *                        lane   rlglue/agent/SwimmerAgent.py:61-239, rlglue/experiment/SwimmerExperiment.cpp:65-84
  *
  * Layouts (d = 2n+2 observation size, m = n-1 action size):
  *   state, SoA    [d][n_env]   field-major: row f holds field f of every env; fields are
@@ -131,7 +133,8 @@ extern "C" {
 #define SW_FLAG_MODEL_TWIN 4
 
 /* Physical parameters of one swimmer model: SwimmerEnv.__init__ (remy_swimmer_env.py:16-39).
- * max_u is not here: the reference never enforces it (actions are not clipped). */
+ * max_u is not here: the reference never enforces it (actions are not clipped).  (Its RL-Glue agent does clip:
+ * sw_rlglue_ars_run_f64 takes max_u as an argument.) */
 typedef struct sw_params {
     int32_t n;        /* segments */
     int32_t flags;    /* 0, or SW_FLAG_* bits (rollout kernel choice, model choice) */
@@ -621,6 +624,45 @@ int sw_lqr_cacla_run_f64(int32_t ns, int32_t na, int64_t n_agent, int32_t n_iter
                          int32_t cost, const double *params, const double *noise, double *F, double *V, double *state,
                          double *last, int32_t *counters, int32_t *status, double *rec_state, double *rec_action,
                          double *rec_reward, uint8_t *rec_admitted, void *stream);
+
+/* ---- The RL-Glue ARS experiment on the native swimmer (rlglue/agent/SwimmerAgent.py:61-130, :167-239 driven by
+ * rlglue/experiment/SwimmerExperiment.cpp:65-84 on rlglue/environment/SwimmerEnvironment.cpp): whole training runs of
+ * many independent agents in ONE launch, one agent per lane ----
+ * sw_rlglue_ars_run_f64 runs n_iter iterations for n_agent agents with N directions, b of them used, segments of H
+ * environment steps.  d = 2n + 2, m = n - 1, s0 = the start state (every component 0.001, SwimmerEnvironment.cpp:41),
+ * clip = the agent's `if a > max_u: a = max_u elif a < -max_u: a = -max_u` (SwimmerAgent.py:192-196; a NaN passes):
+ *   pol(j) = P + nu delta[j / 2] (j even) | P - nu delta[j / 2] (j odd)        (:210-212; delta = np.random.rand)
+ *   before the first iteration: stale = clip(pol(0) s0), total = 0              (agent_start, :61-77)
+ *   segment(W, stale): s = s0 ("load state"), a = stale; for t = 0 .. H - 1: s, r = twin_step(s, a);
+ *         t == 0: first = r, a = clip(W s0)     (the agent answers the first step with the INITIAL observation, :96)
+ *         else:   rest += r, a = clip(W s);      -> first, rest, a (= the next segment's stale action)
+ *   iteration: for j = 0 .. 2N - 1: first, rest, stale = segment(pol(j), stale);
+ *                  rew[(j - 1) mod 2N] = total + first; total = rest            (credited one segment late, :88-93)
+ *              sigma = sample standard deviation of rew[0 .. 2b)                 (:227-231; index order, no sort)
+ *              P += alpha (sum_{i < b} (rew[2i] - rew[2i + 1]) delta[i]) / (b sigma)                      (:233-239)
+ *              first, rest, stale = segment(P, stale); total = rest; report rest (frozen evaluation, :100-104)
+ * So rew[2N - 1] is the evaluation's return before it plus segment 0's first reward, segment 2N - 1's return reaches
+ * no update, and directions b .. N - 1 are rolled out but not used.  Arithmetic is not trapped: NaN and inf propagate
+ * (the reference's statistics.stdev raises on a NaN return; here the agent's status gets SW_STATUS_NONFINITE).
+ * EVERY array is agent-minor ([..][n_agent]):
+ *   alpha, nu     : [n_agent]
+ *   deltas        : [n_iter][N][m][d][n_agent]: the caller's draws for the iterations of THIS call
+ *   policy        : in/out [m][d][n_agent]
+ *   carry         : in/out [m + 1][n_agent]: the stale action, then total; iter_begin == 0 ignores it on input (the
+ *                   kernel forms clip(pol(0) s0) itself)
+ *   eval_returns  : [n_iter][n_agent]: the line SwimmerExperiment.cpp:83 writes
+ *   train_returns : [n_iter][2N][n_agent]: rew as the update saw it (required: the lane reads its own values back)
+ *   status        : in/out int32 [n_agent], |= SW_STATUS_SINGULAR / SW_STATUS_NONFINITE (a state, a return or a
+ *                   policy entry was not finite) / SW_STATUS_RANGE (values are NOT replaced by NaN here)
+ * Everything an agent carries is in/out, so a run can be split into launches and the split changes no bit.  max_u is
+ * an argument, not a field of sw_params; +inf means no clip.  p must carry SW_FLAG_MODEL_TWIN.
+ * Errors, before any HIP call: NULL pointer SW_ERR_NULL; n_agent < 1, n_agent > 2^31 - 1, n_iter < 0, iter_begin < 0,
+ * N < 1, b < 1, b > N (the reference raises IndexError) or H < 1 SW_ERR_SIZE; n outside 2..8 SW_ERR_SEGMENTS; model
+ * bit clear, or max_u NaN or negative SW_ERR_PARAM.  n_iter = 0 writes nothing. */
+int sw_rlglue_ars_run_f64(const sw_params *p, double max_u, int64_t n_agent, int64_t iter_begin, int32_t n_iter,
+                          int32_t N, int32_t b, int32_t H, const double *alpha, const double *nu,
+                          const double *deltas, double *policy, double *carry, double *eval_returns,
+                          double *train_returns, int32_t *status, void *stream);
 
 /* The same update reading an all-gathered buffer in place (no repacking between the
  * collective and the update):  gathered = `world` segments of

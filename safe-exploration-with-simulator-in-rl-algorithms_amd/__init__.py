@@ -17,6 +17,9 @@ Public surface (mirrors the reference's module layout for this path):
     envs.gym_lqr.lqr_env.*                    envs/gym_lqr/lqr_env.py  (host NumPy)
     cacla.lqr_experiment / cacla.safe_exploration_lqr / cacla.window
                                               cacla/lqr_experiment.py, cacla/safe_exploration_lqr.py, cacla/window.py
+    rlglue.Parameters / rlglue.SwimmerExperiment / rlglue.SwimmerExperimentBatch
+                                              rlglue/parameters.txt, rlglue/agent/SwimmerAgent.py under
+                                              rlglue/experiment/SwimmerExperiment.cpp  (whole runs in one launch, twin model)
     kernels.*                                 thin wrappers of the C ABI (include/swimmer_hip.h)
 """
 from . import _build, _lib, kernels  # noqa: F401
@@ -26,6 +29,7 @@ from .ars import (ARSAgent, ARSAgentBatch, ARSParam, EnvParam, Environment, Esti
                   SafeARSAgentBatch)
 from . import safe_ars  # noqa: F401
 from . import cacla  # noqa: F401
+from . import rlglue  # noqa: F401
 
 __all__ = ["SwParams", "SwimmerHipError", "SwimmerEnv", "VecSwimmerEnv", "ARSAgent", "ARSAgentBatch", "SafeARSAgentBatch", "ARSParam",
            "EnvParam", "Environment", "EstimatorBatch", "Experiment", "kernels"]

@@ -145,6 +145,8 @@ _PROTOTYPES = {
                               + [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 9),
     "sw_lqr_cacla_run_f64": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 4
                              + [ctypes.c_void_p] * 13),
+    "sw_rlglue_ars_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int64, ctypes.c_int64]
+                              + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 9),
     "sw_traj_moments_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sw_cov_acc_doubles": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32]),

@@ -858,3 +858,13 @@ def lqr_cacla_run(ns: int, na: int, n_iter: int, safe: bool, threshold: int, cos
                                       ptr(params), ptr(noise), ptr(F), ptr(V), ptr(state), ptr(last), ptr(counters),
                                       ptr(status), ptr(rec_state), ptr(rec_action), ptr(rec_reward),
                                       ptr(rec_admitted), stream_ptr()), "sw_lqr_cacla_run_f64")
+
+
+def __getattr__(name):
+    """kernels.rlglue_ars_run: the checked wrapper of sw_rlglue_ars_run_f64.  It lives next to the classes that use it
+    (rlglue/kernels.py, as cacla/safe_kernels.py and ars/ensemble_kernels.py do) and is reachable from here under the
+    name its siblings have."""
+    if name == "rlglue_ars_run":
+        from .rlglue.kernels import rlglue_ars_run
+        return rlglue_ars_run
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
