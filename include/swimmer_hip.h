@@ -51,6 +51,8 @@
  *                        hyper-parameter grid at once   cacla/cacla_agent.py:19-58, :135-199, cacla/swimmer_experiment.py:21-57
  *   sw_cacla_safe_run_f64  the same learner behind the simulator gate of the safe agents (the combination the
  *                        reference does not have)   cacla/cacla_safe_agent.py:161-188, safe_ars/ars.py:111-122
+ *   sw_cacla_safe_ensemble_run_f64  the same with the gate in an ensemble of up to 64 simulators per agent (where the
+ *                        reference leaves `# TODO compute sim_threshold`)   ars/ars_agent.py:59-70
  *   sw_lqr_cacla_run_f64 CACLA_LQR_agent.run and the safe agents' run loops on the LQR environments, one agent per
  *                        lane   cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py, envs/gym_lqr/lqr_env.py
  *   sw_rlglue_ars_run_f64  SwimmerARSAgent under SwimmerExperiment's loop on the native swimmer, one agent per
@@ -570,6 +572,45 @@ int sw_cacla_safe_run_f64(const sw_params *real, int64_t n_agent, int32_t n_iter
                           double *weights, double *state, double *last_reward, double *rewards,
                           int32_t *admitted_rec, int32_t *counters, int32_t *first_refused,
                           int32_t *status, void *stream);
+
+/* ---- CACLA on the swimmer, every step gated on an ENSEMBLE of simulators: sw_cacla_safe_run_f64 with the look-ahead
+ * in n_member simulators per agent (the CACLA side of sw_ars_gate_ensemble_f64: the members stand for the uncertainty
+ * about (l_i, m_i, k), and a step is taken only where every one of them admits it) ----
+ * sw_cacla_safe_ensemble_run_f64 runs n_iter steps for n_agent agents, one wave each, always training.  The members
+ * ride in the lanes of the agent's wave -- lane L looks ahead in member L % n_member -- so an agent has at most 64 of
+ * them: MORE THAN ONE WAVE'S WORTH OF MEMBERS IS NOT BUILT.  Step t of a gated agent:
+ *   FA_act = actors(state); action = FA_act + noise[t]   (consumed whether or not the step is taken)
+ *   c_e = cost(step(state, action) with member e's constants)     for every member e (n, h, direction are `real`'s)
+ *   admitted = c_e <= sim_thresh[a] for EVERY e           (a NaN cost or threshold refuses)
+ *   admitted / refused: as sw_cacla_safe_run_f64, and so are rewards, last_reward, counters, first_refused, t_begin and
+ *             the status bits
+ * With n_member = 1, or with n_member copies of one simulator, every output has the bits of sw_cacla_safe_run_f64 in
+ * that simulator; an agent with gated[a] == 0 reads neither sims nor sim_thresh and has the bits of
+ * sw_cacla_run_f64(train = 1).  The order of an agent's members changes nothing but the order of member_refusals.
+ *   real, gamma, alpha, noise, gated, sim_thresh, real_thresh, cost_kind, cost_index, weights, state, last_reward,
+ *   rewards, admitted_rec, counters, first_refused, status : as sw_cacla_safe_run_f64
+ *   n_member      : 1..64, the same for every agent
+ *   sims          : [n_agent][n_member][3] (l_i, m_i, k) of each member, read for gated agents only; the constants are
+ *                   derived in the kernel by the function the host uses
+ *   worst_rec     : NULL or [n_agent][n_iter]: the largest member cost of step t, admitted or refused; a NaN cost or a
+ *                   member that breaks the parameter rule counts as +inf (NaN -> +inf per member first, then the
+ *                   maximum: exact in any order).  On an admitted step worst_rec <= sim_thresh, on a refused one it is
+ *                   larger (or the threshold is NaN).  NaN for an ungated agent
+ *   member_refusals : NULL or in/out [n_agent][n_member], += the steps at which member e's own cost was not
+ *                   <= sim_thresh, whatever the other members said (which member binds); zero it before a run.
+ *                   Untouched for an ungated agent
+ * A gated agent with a member that breaks the parameter rule (SW_ERR_PARAM's) gets SW_STATUS_PARAM and every step
+ * refused (that member's constants are not used; its refusals count every step, worst_rec is +inf); the other agents
+ * are unaffected.  A run can be split into launches as with sw_cacla_safe_run_f64, and the split changes no bit.
+ * Errors, before any HIP call: those of sw_cacla_safe_run_f64 (worst_rec and member_refusals may be NULL as well), and
+ * n_member < 1 or n_member > 64 SW_ERR_SIZE.  n_iter = 0 writes nothing. */
+int sw_cacla_safe_ensemble_run_f64(const sw_params *real, int64_t n_agent, int32_t n_member, int32_t n_iter,
+                                   int64_t t_begin, const double *gamma, const double *alpha, const double *noise,
+                                   const int32_t *gated, const double *sims, const double *sim_thresh,
+                                   const double *real_thresh, int32_t cost_kind, int32_t cost_index, double *weights,
+                                   double *state, double *last_reward, double *rewards, int32_t *admitted_rec,
+                                   double *worst_rec, int32_t *member_refusals, int32_t *counters,
+                                   int32_t *first_refused, int32_t *status, void *stream);
 
 /* ---- CACLA on LQR, with and without safe exploration (cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py,
  * envs/gym_lqr/lqr_env.py): whole runs of many independent agents in ONE launch, one agent per lane ----

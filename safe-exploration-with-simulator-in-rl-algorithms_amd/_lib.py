@@ -143,6 +143,10 @@ _PROTOTYPES = {
                          + [ctypes.c_void_p] * 9),
     "sw_cacla_safe_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]
                               + [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 9),
+    # the same gate in an ensemble of simulators per agent, the members in the lanes of the agent's wave
+    "sw_cacla_safe_ensemble_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                      ctypes.c_int64] + [ctypes.c_void_p] * 7
+                                       + [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 11),
     "sw_lqr_cacla_run_f64": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 4
                              + [ctypes.c_void_p] * 13),
     "sw_rlglue_ars_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int64, ctypes.c_int64]

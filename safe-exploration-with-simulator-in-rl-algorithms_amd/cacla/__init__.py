@@ -7,7 +7,9 @@ in registers, whole runs in one launch).
 
 Swimmer with safe exploration (the combination the reference stops short of): `CACLA_SE_agent`, `CACLA_SE_Batch`
 and `swimmer_experiment.safe_compare` -- the same learner behind a per-step simulator gate, on the fused kernel behind
-sw_cacla_safe_run_f64.
+sw_cacla_safe_run_f64.  With `sim_ensemble=` / `sim_ensembles=`, and in `swimmer_experiment.safe_compare_ensemble`, the
+gate runs in an ensemble of up to 64 simulators per agent, the members in the lanes of the agent's wave
+(sw_cacla_safe_ensemble_run_f64), and a step is taken only where every member admits it.
 
 LQR (cacla/cacla_agent.py:202-297, cacla/cacla_safe_agent.py, cacla/lqr_experiment.py,
 cacla/safe_exploration_lqr.py, cacla/window.py): `CACLA_LQR_agent`, the safe agents of `cacla_safe_agent`,

@@ -44,3 +44,42 @@ def cacla_safe_run(p: SwParams, n_iter: int, t_begin: int, gamma, alpha, noise, 
                                        ptr(rewards), ptr(admitted_rec), ptr(counters), ptr(first_refused), ptr(status),
                                        stream_ptr()), "sw_cacla_safe_run_f64")
     return rewards
+
+
+def cacla_safe_ensemble_run(p: SwParams, n_iter: int, t_begin: int, gamma, alpha, noise, gated, sims, sim_thresh,
+                            real_thresh, cost_kind: int, cost_index: int, weights, state, last_reward, counters,
+                            first_refused, rewards=None, admitted_rec=None, worst_rec=None, member_refusals=None,
+                            status=None):
+    """cacla_safe_run with every step gated on an ENSEMBLE of simulators (sw_cacla_safe_ensemble_run_f64): sims
+    [A, E, 3] rows (l_i, m_i, k), the same E for every agent, at most 64 (the library's SW_ERR_SIZE beyond), and a
+    step is taken only where every member admits it.  Everything else as cacla_safe_run; besides, when given,
+    worst_rec [A, n_iter] is written (the largest member cost of each step, NaN or a bad member as +inf; NaN for an
+    ungated agent) and member_refusals int32 [A, E] (zero before a run) accumulates the steps at which each member's
+    own cost was not <= sim_thresh.  Returns `rewards` [A, n_iter]."""
+    require_gpu()
+    on = _gpu(gamma, "gamma", 1)
+    A = _tensor(gamma, "gamma", (_Min(1),), on).shape[0]
+    _tensor(alpha, "alpha", (A,), on)
+    _tensor(noise, "noise", (A, n_iter, p.m), on)
+    _tensor(gated, "gated", (A,), on, _I32)
+    E = _tensor(sims, "sims", (A, _Min(1), 3), on).shape[1]
+    _tensor(sim_thresh, "sim_thresh", (A,), on)
+    _tensor(real_thresh, "real_thresh", (A,), on)
+    _tensor(weights, "weights", (A, p.n, cacla_net_doubles(p.n)), on)
+    _tensor(state, "state", (A, p.d), on)
+    _tensor(last_reward, "last_reward", (A,), on)
+    _tensor(counters, "counters", (A, 3), on, _I32)
+    _tensor(first_refused, "first_refused", (A,), on, _I32)
+    _opt(admitted_rec, "admitted_rec", (A, n_iter), on, _I32)
+    _opt(worst_rec, "worst_rec", (A, n_iter), on)
+    _opt(member_refusals, "member_refusals", (A, E), on, _I32)
+    _opt(status, "status", (A,), on, _I32)
+    rewards = _out(rewards, "rewards", (A, n_iter), on)
+    check(load().sw_cacla_safe_ensemble_run_f64(ctypes.byref(p), A, E, int(n_iter), int(t_begin), ptr(gamma),
+                                                ptr(alpha), ptr(noise), ptr(gated), ptr(sims), ptr(sim_thresh),
+                                                ptr(real_thresh), int(cost_kind), int(cost_index), ptr(weights),
+                                                ptr(state), ptr(last_reward), ptr(rewards), ptr(admitted_rec),
+                                                ptr(worst_rec), ptr(member_refusals), ptr(counters),
+                                                ptr(first_refused), ptr(status), stream_ptr()),
+          "sw_cacla_safe_ensemble_run_f64")
+    return rewards

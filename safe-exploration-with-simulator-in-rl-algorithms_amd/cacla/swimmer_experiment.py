@@ -97,6 +97,43 @@ def safe_compare(env, sim, gamma, alpha, sigma, seeds, cost, real_threshold, sim
                 first_refused=batch.first_refused[S:].copy())
 
 
+def safe_compare_ensemble(env, ensemble, gamma, alpha, sigma, seeds, cost, real_threshold, n_iter, sim_threshold=None,
+                          chunk=2048):
+    """Plain, gated on one simulator and gated on an ensemble of simulators from the same seeds: per seed one ungated
+    agent, one gated on member 0 of `ensemble` alone (as E copies of it: the ensemble kernel then has the single
+    kernel's bits) and one gated on all E members -- all three in ONE CACLA_SE_Batch.  `ensemble` is what
+    CACLA_SE_agent's sim_ensemble takes; sim_threshold None is the real threshold itself.
+
+    Returns a dict: rewards_*, admitted_*, violations_* and first_refused_* (-1: nothing refused) for plain / single /
+    ensemble ([n_seed, n_iter] the rewards, [n_seed] the rest), member_refusals [n_seed, E] (the ensemble agents':
+    which member binds) and worst_margin [n_seed]: the smallest sim_threshold - worst_cost over the ensemble agent's
+    admitted steps, +inf where none was admitted -- how close the worst member came to the threshold."""
+    from .cacla_safe_swimmer import CACLA_SE_Batch, _ensemble, member_rows
+    rows = member_rows(env, _ensemble(ensemble))
+    seeds = [int(s) for s in seeds]
+    S, E = len(seeds), len(rows)
+    if S < 1:
+        raise ValueError("safe_compare_ensemble needs at least one seed")
+    if sim_threshold is None:
+        sim_threshold = real_threshold
+    members = np.concatenate([np.tile(rows[:1], (2 * S, E, 1)), np.tile(rows, (S, 1, 1))])
+    batch = CACLA_SE_Batch(env, [gamma] * 3 * S, [alpha] * 3 * S, [sigma] * 3 * S, seeds * 3, None,
+                           [sim_threshold] * 3 * S, [real_threshold] * 3 * S, cost, gated=[0] * S + [1] * 2 * S,
+                           sim_ensembles=members)
+    rewards, admitted = batch.run(n_iter, chunk=chunk)
+    out = {}
+    for i, who in enumerate(("plain", "single", "ensemble")):
+        part = slice(i * S, (i + 1) * S)
+        out["rewards_" + who] = rewards[part]
+        out["admitted_" + who] = batch.admitted[part].copy()
+        out["violations_" + who] = batch.violations[part].copy()
+        out["first_refused_" + who] = batch.first_refused[part].copy()
+    out["member_refusals"] = batch.member_refusals[2 * S:].copy()
+    margin = np.where(admitted[2 * S:], float(sim_threshold) - batch.worst_cost[2 * S:], np.inf)
+    out["worst_margin"] = margin.min(axis=1, initial=np.inf)
+    return out
+
+
 def experience(env, gamma, alpha, sigma, n_iter, H=1000, n_seed=3, out_dir="results/cacla/"):
     """One setting of the grid (swimmer_experiment.py:21-44): (t, mean, std) of its n_seed agents."""
     mean, std = grid(env, [gamma], [alpha], [sigma], n_iter, n_seed=n_seed, out_dir=out_dir, H=H)[(gamma, alpha, sigma)]

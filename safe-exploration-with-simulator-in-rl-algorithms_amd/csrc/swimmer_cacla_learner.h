@@ -1,7 +1,8 @@
 // swimmer_cacla_learner.h -- the CACLA learner on the swimmer (cacla/cacla_agent.py:135-199), ONE WAVE PER AGENT: what
-// cacla_kernel (swimmer_cacla.hip) and cacla_safe_kernel (swimmer_cacla_safe.hip) both run.  The two kernels call the
-// pieces below in the same order, so an ungated agent of sw_cacla_safe_run_f64 has the bits of
-// sw_cacla_run_f64(train = 1) by construction (tests/test_cacla_safe_gpu.py holds them to it at every n).
+// cacla_kernel (swimmer_cacla.hip), cacla_safe_kernel (swimmer_cacla_safe.hip) and cacla_ensemble_kernel
+// (swimmer_cacla_ensemble.hip) all run.  The kernels call the pieces below in the same order, so an ungated agent of
+// sw_cacla_safe_run_f64 or sw_cacla_safe_ensemble_run_f64 has the bits of sw_cacla_run_f64(train = 1) by construction
+// (tests/test_cacla_safe_gpu.py and tests/test_cacla_ensemble_gpu.py hold them to it at every n).
 //
 // One step (cacla_agent.py:170-193): actor forward, Gaussian action, physics step, critic at the new and at the old
 // state, SGD step on the critic, SGD step on the actors when the temporal difference is positive.  No clipping, no

@@ -79,7 +79,7 @@
 //   swimmer_cov.hip, swimmer_cov.h
 //   traj_moments_kernel<D>     full first/second moments of a trajectory buffer; HBM-bound; its tile code
 //                              (swimmer_cov.h) also rides along in the segment-per-lane rollout launches (SideJob)
-//   swimmer_cacla_learner.h     the CACLA learner of the two files below: the layout of an agent's networks over its
+//   swimmer_cacla_learner.h     the CACLA learner of the three files below: the layout of an agent's networks over its
 //                              wave, weight / state / noise loads and stores, forward<N> and learn<N>
 //   swimmer_cacla.hip (a translation unit of its own)
 //   cacla_kernel<N,TRAIN>      sw_cacla_run_f64: CACLA training runs of many independent agents, n_iter sequential
@@ -93,6 +93,12 @@
 //                              simulator's look-ahead step and the cost redundantly in every lane, the admit decision
 //                              taken from the first lane into a scalar register, the real step and the update behind
 //                              a uniform branch; reward entry and admit flag staged per lane, stored once per block
+//   swimmer_cacla_ensemble.hip (a translation unit of its own)
+//   cacla_ensemble_kernel<N>   sw_cacla_safe_ensemble_run_f64: cacla_safe_kernel's run loop with the look-ahead in an
+//                              ENSEMBLE of up to 64 simulators: lane L holds the constants of member L % n_member in
+//                              VGPRs, so the same instructions look ahead in every member; the admit decision is a wave
+//                              ballot over every lane's verdict; optionally the worst member cost per step (a wave
+//                              maximum behind a uniform branch) and per-member refusal counts
 //   swimmer_lqr.hip (a translation unit of its own)
 //   lqr_cacla_kernel<NS,NA,MODE>  sw_lqr_cacla_run_f64: CACLA on LQR problems (plain, safe with a per-step or a fixed
 //                              simulator threshold), ONE AGENT PER LANE: models, F, V and state in VGPRs, no LDS, no
