@@ -47,6 +47,8 @@
  *   sw_safe_ars_rollouts_multi_f64
  *                        Basic_ARS.rollout / Safe_ARS.rollout for the 2N perturbed policies of every agent of
  *                        safe_ars/experiment.py at once                safe_ars/ars.py:20-31, :111-153, :84-94
+ *   sw_safe_ars_rollouts_ensemble_f64  the same with the per-step gate in an ensemble of up to 64 simulators per agent
+ *                        (where the script has `sim_thresh = thresh - 1`)   safe_ars/experiment.py:59
  *   sw_cacla_run_f64     CACLA_agent.run with TwoLayersNet / ActorFA / CriticFA, for every agent of the
  *                        hyper-parameter grid at once   cacla/cacla_agent.py:19-58, :135-199, cacla/swimmer_experiment.py:21-57
  *   sw_cacla_safe_run_f64  the same learner behind the simulator gate of the safe agents (the combination the
@@ -499,6 +501,44 @@ int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64
                                    int32_t cost_kind, int32_t cost_index, double *returns, double *cost_trace,
                                    double *cost_max, int32_t *first_refused, int32_t *violations, int32_t *status,
                                    void *stream);
+
+/* ---- the same rollouts, every step of a gated agent gated on an ENSEMBLE of simulators (the per-step side of
+ * sw_ars_gate_ensemble_f64 and sw_cacla_safe_ensemble_run_f64: the members stand for the uncertainty about
+ * (l_i, m_i, k), where safe_ars/experiment.py:59 has one simulator and `sim_thresh = thresh - 1`) ----
+ * sw_safe_ars_rollouts_ensemble_f64: sw_safe_ars_rollouts_multi_f64 with n_member simulators per agent.  Every argument
+ * of that function keeps its meaning, layout and NULL rule.  Step t of a rollout of a gated agent:
+ *   u = (P +- nu delta) @ obs
+ *   c_e = cost(step(obs, u) with member e's constants)     for every member e (n, h, direction are `real`'s)
+ *   the step is taken iff c_e <= sim_thresh[a] for EVERY e  (a NaN cost or threshold refuses)
+ *   a refused rollout stops stepping and repeats its state, as in sw_safe_ars_rollouts_multi_f64
+ * The members ride in lanes: a rollout owns a group of G lanes of a wave, G the smallest power of two >= n_member, lane
+ * j with the constants of member j % n_member, and the gate is a wave ballot -- so an agent has at most 64 members:
+ * MORE THAN ONE WAVE'S WORTH OF MEMBERS IS NOT BUILT.  One kernel form for every n = 2..8, one rollout group per
+ * 64 / G of a 64-thread workgroup, grid (ceil(2 n_dir G / 64), n_agent); SW_FLAG_ROLLOUT_* is accepted and ignored.  A
+ * MIRROR-QUAD ENSEMBLE FORM FOR n = 3 AND A ROW FORM ARE NOT BUILT.  The arithmetic is that of the lane form: with
+ * n_member = 1, or with n_member copies of one simulator, every output the two functions share has the bits of
+ * sw_safe_ars_rollouts_multi_f64 under SW_FLAG_ROLLOUT_LANE in that simulator, and an agent with gated[a] == 0 (which
+ * reads neither sims nor sim_thresh) has that function's ungated bits.  The order of an agent's members changes nothing
+ * but the order of the bits of refusing_members.
+ *   n_member      : 1..64, the same for every agent
+ *   sims          : [n_agent][n_member][3] (l_i, m_i, k) of each member, read for gated agents only; the constants are
+ *                   derived in the kernel by the function the host uses
+ *   worst_max     : NULL or [n_agent][2 n_dir]: the maximum of c_e over the ADMITTED steps and over all e, so never
+ *                   above sim_thresh; 0 where no step was admitted (costs are >= 0); NaN for an ungated agent
+ *   refusing_members : NULL or [n_agent][2 n_dir]: bit e set iff member e's own cost was not <= sim_thresh at the first
+ *                   refused step (which member binds); 0 where no step was refused and for an ungated agent
+ * A gated agent with a member that breaks the parameter rule (SW_ERR_PARAM's) gets SW_STATUS_PARAM, NaN returns,
+ * cost_trace, cost_max and worst_max, first_refused 0, no violations and the bits of the bad members in
+ * refusing_members; the other agents are unaffected.  Only lane 0 of a group stores, with plain stores: no result
+ * depends on timing.
+ * Errors, before any HIP call: those of sw_safe_ars_rollouts_multi_f64 (worst_max and refusing_members may be NULL);
+ * n_member < 1, n_member > 64 or 2^32 threads and more (64 per 64 / G rollouts) SW_ERR_SIZE; twin model SW_ERR_PARAM. */
+int sw_safe_ars_rollouts_ensemble_f64(const sw_params *real, int64_t n_agent, int32_t n_member, int64_t n_dir, int32_t H,
+                                      const double *policy, const double *deltas, double nu, const int32_t *gated,
+                                      const double *sims, const double *sim_thresh, const double *real_thresh,
+                                      int32_t cost_kind, int32_t cost_index, double *returns, double *cost_trace,
+                                      double *cost_max, int32_t *first_refused, int32_t *violations, int32_t *status,
+                                      double *worst_max, int64_t *refusing_members, void *stream);
 
 /* ---- CACLA (cacla/cacla_agent.py): whole training runs of many independent agents in ONE launch ----
  * An agent is n networks -- the n - 1 actors of ActorFA (one per torque), then the critic of CriticFA -- each a

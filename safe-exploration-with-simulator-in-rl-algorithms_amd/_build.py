@@ -16,9 +16,11 @@ OBJ_DIR = LIB_PATH + ".obj"    # a library's objects live next to it: A/B builds
 # swimmer_cacla_safe.hip the same behind the simulator gate (likewise; the learner both run is swimmer_cacla_learner.h),
 # swimmer_cacla_ensemble.hip the gate in an ensemble of simulators, the members in the wave's lanes (likewise),
 # swimmer_lqr.hip CACLA on the LQR problems (a unit of its own as well), swimmer_rlglue_ars.hip the RL-Glue ARS
-# experiment on the twin model (likewise)
+# experiment on the twin model (likewise), swimmer_safe_ars_ensemble.hip the safe-ARS rollouts gated on an ensemble of
+# simulators (likewise; its body is swimmer_rollout_safe_lane.inc)
 SOURCES = ["swimmer_kernels.hip", "swimmer_abi.hip", "swimmer_cacla.hip", "swimmer_lqr.hip", "swimmer_cacla_safe.hip",
-           "swimmer_cacla_ensemble.hip", "swimmer_rlglue_ars.hip", "direct_comm.cpp", "host_rng.cpp"]
+           "swimmer_cacla_ensemble.hip", "swimmer_rlglue_ars.hip", "swimmer_safe_ars_ensemble.hip", "direct_comm.cpp",
+           "host_rng.cpp"]
 FAMILIES = ["swimmer_rollout_row.hip", "swimmer_rollout_n3.hip", "swimmer_rollout_lane.hip",
             "swimmer_rollout_safe_multi.hip", "swimmer_step.hip", "swimmer_cov.hip", "swimmer_update.hip"]
 HOST_ONLY = {"host_rng.cpp"}   # plain C++, no device pass: it picks its vector width from the CPU's features at

@@ -139,6 +139,12 @@ _PROTOTYPES = {
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
                                        + [ctypes.c_void_p] * 4 + [ctypes.c_int32, ctypes.c_int32]
                                        + [ctypes.c_void_p] * 7),
+    # the same with the per-step gate in an ensemble of simulators per agent, a rollout in a group of lanes
+    "sw_safe_ars_rollouts_ensemble_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                         ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_double]
+                                          + [ctypes.c_void_p] * 4 + [ctypes.c_int32, ctypes.c_int32]
+                                          + [ctypes.c_void_p] * 9),
     "sw_cacla_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
                          + [ctypes.c_void_p] * 9),
     "sw_cacla_safe_run_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]

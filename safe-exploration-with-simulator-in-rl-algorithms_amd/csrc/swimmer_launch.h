@@ -70,6 +70,13 @@
 //                              agent: the safe-exploration bodies (swimmer_rollout_safe_oct3.inc, _lane.inc, shared with
 //                              safe_rollout_oct3_kernel / safe_rollout_kernel) behind swimmer_rollout_safe_multi.inc;
 //                              per step one cost value per rollout instead of a trajectory
+//   swimmer_safe_ars_ensemble.hip (a translation unit of its own)
+//   safe_ars_ensemble_kernel<N>  sw_safe_ars_rollouts_ensemble_f64: the lane body of the kernels above
+//                              (swimmer_rollout_safe_lane.inc with SW_SAFE_ENSEMBLE 1) with a rollout in a GROUP of
+//                              2^k >= n_member lanes, lane j with the constants of member j % n_member of the agent's
+//                              simulator ensemble in VGPRs: the look-ahead of every member in the same instructions,
+//                              the gate a wave ballot cut to the group, which also names the refusing members; the
+//                              worst admitted member cost a per-lane running maximum, reduced once behind the loop
 //   swimmer_update.hip
 //   ars_update_kernel          sigma_R, policy step, V2 statistics merge; pure latency between
 //                              two rollout launches: one round of loads, then LDS only

@@ -4,9 +4,16 @@
 // per-agent view: the policy is P + / - nu delta, `gated` -- workgroup-uniform -- decides whether the rollout looks
 // ahead at all, and the cost of the state the reference appends at step t goes to cost_trace / cost_max instead of the
 // state to a trajectory).
+// SW_SAFE_ENSEMBLE 1 (with SW_SAFE_MULTI 1; sw_safe_ars_rollouts_ensemble_f64, csrc/swimmer_safe_ars_ensemble.hip): a
+// rollout owns a GROUP of lanes, each with the constants of one member of the agent's simulator ensemble in Csim.  The
+// kernel has placed the lane already -- r, and `owner`, the one lane of the group that stores -- and the gate is a wave
+// ballot over the group: `member_bits` (kernel) cuts this group's members out of it.  A group leaves the loop whole.
     constexpr int D = 2 * N + 2, M = N - 1;
+#if !SW_SAFE_ENSEMBLE
     const int64_t r = (int64_t)blockIdx.x * kRollBlock + threadIdx.x;
     if (r >= n_roll) return;
+    constexpr bool owner = true;
+#endif
     double W[M][D];
 #if SW_SAFE_MULTI
     {   // P + / - nu delta with NumPy's rounding (rollout_kernel's prologue, swimmer_rollout_lane.inc)
@@ -18,7 +25,7 @@
             for (int j = 0; j < D; ++j) W[i][j] = __dadd_rn(policies[i * D + j], sgn * __dmul_rn(nu, dl[i * D + j]));
     }
     double cnow = 0.0, cmax = 0.0;                    // cost of the current state; costs are >= 0 or NaN
-    double *const trace = all.cost_trace ? all.cost_trace + agent * n_roll + r : nullptr;
+    double *const trace = (owner && all.cost_trace) ? all.cost_trace + agent * n_roll + r : nullptr;
     const int64_t trace_step = (int64_t)gridDim.y * n_roll;   // cost_trace [H][n_agent][n_roll], grid.y = n_agent
     auto nan_max = [](double a, double b) { return __builtin_isunordered(a, b) ? __builtin_nan("") : fmax(a, b); };
 #else
@@ -85,10 +92,22 @@
             sthd[i] = thd[i];
         }
         (void)sw::euler_step<N>(Csim, sgx, sgy, sth, sthd, u, srew);
+#if SW_SAFE_ENSEMBLE
+        // every lane its member's verdict; the group's through one ballot: all of its lanes see the same bits
+        const double c_mem = safe_cost<N>(cost_kind, cost_index, sgx, sgy, sth, sthd);
+        const uint64_t out = member_bits(__builtin_amdgcn_ballot_w64(!(c_mem <= sim_thresh)));   // NaN refuses
+        if (out) {
+            refused_at = t;
+            refusing = out;
+            break;
+        }
+        if (want_worst) worst = fmax(worst, c_mem);   // uniform; an admitted cost is no NaN
+#else
         if (!(safe_cost<N>(cost_kind, cost_index, sgx, sgy, sth, sthd) <= sim_thresh)) {   // :122, NaN refuses
             refused_at = t;
             break;
         }
+#endif
 #if SW_SAFE_MULTI
         }
 #endif
@@ -112,7 +131,7 @@
         if (trace)
             for (int32_t t = refused_at; t < H; ++t) trace[t * trace_step] = cnow;
     }
-    if (cost_max) cost_max[r] = cmax;
+    if (owner && cost_max) cost_max[r] = cmax;
 #else
     if (traj)
         for (int32_t t = refused_at; t < H; ++t) record(t);      // :151: the unchanged state, step after step
@@ -121,8 +140,11 @@
 #pragma unroll
     for (int i = 0; i < N; ++i) fin = fin && isfinite(th[i]) && isfinite(thd[i]);
     const bool in_range = thmax < sw::kAngleLimit;
-    returns[r] = in_range ? total : __builtin_nan("");
-    if (first_refused) first_refused[r] = refused_at;
-    if (violations) violations[r] = over;
-    if (status)
-        status[r] = (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) | (in_range ? 0 : SW_STATUS_RANGE);
+    if (owner) {
+        returns[r] = in_range ? total : __builtin_nan("");
+        if (first_refused) first_refused[r] = refused_at;
+        if (violations) violations[r] = over;
+        if (status)
+            status[r] =
+                (ok ? 0 : SW_STATUS_SINGULAR) | (fin ? 0 : SW_STATUS_NONFINITE) | (in_range ? 0 : SW_STATUS_RANGE);
+    }

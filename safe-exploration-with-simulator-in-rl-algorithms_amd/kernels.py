@@ -863,8 +863,11 @@ def lqr_cacla_run(ns: int, na: int, n_iter: int, safe: bool, threshold: int, cos
 def __getattr__(name):
     """kernels.rlglue_ars_run: the checked wrapper of sw_rlglue_ars_run_f64.  It lives next to the classes that use it
     (rlglue/kernels.py, as cacla/safe_kernels.py and ars/ensemble_kernels.py do) and is reachable from here under the
-    name its siblings have."""
+    name its siblings have.  kernels.safe_ars_rollouts_ensemble (safe_ars/ensemble_kernels.py) likewise."""
     if name == "rlglue_ars_run":
         from .rlglue.kernels import rlglue_ars_run
         return rlglue_ars_run
+    if name == "safe_ars_rollouts_ensemble":
+        from .safe_ars.ensemble_kernels import safe_ars_rollouts_ensemble
+        return safe_ars_rollouts_ensemble
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -6,6 +6,8 @@ agent trained from the same seed -- here all 2 n_seeds agents as ONE `ARSBatch`.
         --alpha 0.02 --nu 0.03 --path ./ --n_seeds 10
 
 `run` returns what the script accumulates and plots; `main` takes the script's ten flags and saves its figure.
+`run_ensemble` adds a third agent per seed, gated on an ensemble of simulators on the epsilon-sphere around the estimate
+(where the script has one simulator and `sim_thresh = thresh - 1`, :59), all 3 n_seeds agents in one batch.
 """
 import argparse
 
@@ -67,6 +69,55 @@ def run(epsilon, thresh, n_iter, n_rollout, N, b, alpha, nu, n_seeds, seeds=None
         out[f"mean_{kind}_returns"] = np.mean(out[f"{kind}_returns"], axis=0)
         out[f"mean_{kind}_costs"] = np.mean(out[f"{kind}_costs"], axis=0)
         out[f"std_{kind}_returns"] = np.std(out[f"{kind}_returns"], axis=0)
+    return out
+
+
+def ensemble_members(theta_sim, epsilon, n_sim, ensemble_seed=0):
+    """[n_sim, 3] (m_i, l_i, k): member 0 is theta_sim, member i >= 1 theta_sim + epsilon g / ||g||_2 with
+    g = RandomState(ensemble_seed).standard_normal(3) drawn in member order -- samples on the epsilon-sphere around the
+    estimate, the sphere that holds the real swimmer by construction.  No global generator is touched."""
+    n_sim = int(n_sim)
+    if n_sim < 1:
+        raise ValueError("ensemble_members needs n_sim >= 1")
+    rs = np.random.RandomState(ensemble_seed)
+    rows = [np.asarray(theta_sim, dtype=np.float64)]
+    for _ in range(1, n_sim):
+        g = rs.standard_normal(3)
+        rows.append(rows[0] + epsilon * (g / np.linalg.norm(g, ord=2)))
+    return np.array(rows)
+
+
+def run_ensemble(epsilon, thresh, n_iter, n_rollout, N, b, alpha, nu, n_seeds, n_sim, seeds=None, theta_sim=None,
+                 ensemble_seed=0, sim_thresh=None, device=None):
+    """The experiment with a third agent per seed, gated on an ENSEMBLE of n_sim simulators (ensemble_members) at
+    sim_thresh (default: `thresh` itself) where the script's safe agent is gated on one simulator at `thresh - 1`.  Per
+    seed a basic agent, the script's safe agent (n_sim copies of member 0) and the ensemble agent train in ONE ARSBatch
+    (agents 3i, 3i + 1, 3i + 2), so setup and seeds are drawn as `run` draws them.  Returns run's keys for the first two
+    -- the bits of run(..., rollout_kernel="lane") on the same seeds and theta_sim -- and for the ensemble agent
+    ensemble_returns [n_seeds, n_iter], ensemble_costs [n_seeds, 2 n_iter n_rollout], ensemble_violations [n_seeds],
+    member_refusals [n_seeds, n_sim] (the rollouts in which member e was among those that refused), worst_margin (the
+    simulator threshold minus the largest member cost of any admitted step of the ensemble agents: how far the worst
+    member stayed from the threshold; the threshold itself where nothing was admitted) and `members` [n_sim, 3]."""
+    theta_sim, seeds = draw_setup(epsilon, n_iter, N, n_seeds, seeds, theta_sim)
+    sim_thresh = thresh if sim_thresh is None else sim_thresh
+    kw = {} if device is None else {"device": device}
+    real_env = SwimmerEnv("RealWorld", n=N_SEGMENTS, m_i=THETA_REAL[0], l_i=THETA_REAL[1], k=THETA_REAL[2], **kw)
+    members = ensemble_members(theta_sim, epsilon, n_sim, ensemble_seed)
+    sims = [SwimmerEnv("Simulator", n=N_SEGMENTS, m_i=row[0], l_i=row[1], k=row[2], **kw) for row in members]
+    batch = ARSBatch(real_env, [s for s in seeds for _ in range(3)], [False, True, True] * n_seeds, MaxAbsThetaDot(),
+                     real_thresh=thresh, sim_thresh=[0.0, thresh - 1, sim_thresh] * n_seeds, device=device,
+                     sim_ensembles=[None, [sims[0]] * len(sims), sims] * n_seeds)
+    curves = batch.train(n_iter, N, b, alpha, nu, n_rollout, costs="reference")
+    out = {"theta_sim": theta_sim, "seeds": seeds, "batch": batch, "members": members}
+    for k, kind in enumerate(("unsafe", "safe", "ensemble")):
+        out[f"{kind}_returns"] = curves[k::3]
+        out[f"{kind}_costs"] = batch.costs[k::3]
+        out[f"{kind}_violations"] = batch.real_violations[k::3]
+        out[f"mean_{kind}_returns"] = np.mean(out[f"{kind}_returns"], axis=0)
+        out[f"mean_{kind}_costs"] = np.mean(out[f"{kind}_costs"], axis=0)
+        out[f"std_{kind}_returns"] = np.std(out[f"{kind}_returns"], axis=0)
+    out["member_refusals"] = batch.member_refusals[2::3]
+    out["worst_margin"] = float(sim_thresh - batch.worst_max[2::3].max())    # worst_max is 0 where nothing was admitted
     return out
 
 
