@@ -14,7 +14,8 @@ OBJ_DIR = LIB_PATH + ".obj"    # a library's objects live next to it: A/B builds
 # they have to be compiled together), swimmer_abi.hip is the rollout entry points and the ARS pipeline,
 # swimmer_cacla.hip CACLA on the swimmer (a unit of its own: nothing in it is shared with the families),
 # swimmer_cacla_safe.hip the same behind the simulator gate (likewise; the learner both run is swimmer_cacla_learner.h),
-# swimmer_cacla_ensemble.hip the gate in an ensemble of simulators, the members in the wave's lanes (likewise),
+# swimmer_cacla_ensemble.hip the gate in an ensemble of simulators, the members in the wave's lanes (likewise; the one
+# kernel body, argument check and launch of these two is swimmer_cacla_gated.h, each unit instantiating its own seven),
 # swimmer_lqr.hip CACLA on the LQR problems (a unit of its own as well), swimmer_rlglue_ars.hip the RL-Glue ARS
 # experiment on the twin model (likewise), swimmer_safe_ars_ensemble.hip the safe-ARS rollouts gated on an ensemble of
 # simulators (likewise; its body is swimmer_rollout_safe_lane.inc)
@@ -31,7 +32,7 @@ HEADERS = ["rlglue_env.cpp", os.path.join("..", "..", "include", "rlglue_swimmer
            "swimmer_rollout_row.inc", "swimmer_rollout_multi.inc", "swimmer_rollout_safe_oct3.inc",
            "swimmer_rollout_safe_lane.inc", "swimmer_rollout_safe_multi.inc", "swimmer_update.inc", "swimmer_quad3.h",
            "swimmer_oct3.h", "swimmer_row.h", "swimmer_row_fused.h", "swimmer_twin.h", "swimmer_cacla_learner.h",
-           os.path.join("..", "..", "include", "swimmer_hip.h")] + FAMILIES
+           "swimmer_cacla_gated.h", os.path.join("..", "..", "include", "swimmer_hip.h")] + FAMILIES
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + os.environ.get("SWIMMER_HIPCC_EXTRA", "").split()
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC"]
 LINK_LIBS = ["-ldl"]   # direct_comm.cpp resolves RCCL at run time

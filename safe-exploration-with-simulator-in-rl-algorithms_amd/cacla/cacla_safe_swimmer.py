@@ -102,26 +102,20 @@ class _SafeRun(object):
             self.worst_cost = np.empty((self.A, 0)) if self.ensemble else None
             return np.empty((self.A, 0)), np.empty((self.A, 0), dtype=bool)
 
-        def launch_ensemble(c, t, noise):
-            rec = torch.empty((self.A, c), dtype=torch.int32, device=self.device)
-            worst = torch.empty((self.A, c), dtype=torch.float64, device=self.device)
-            return safe_kernels.cacla_safe_ensemble_run(
-                self.p, c, t, self.gamma, self.alpha, noise, self.gated, self.sim, self.sim_thresh, self.real_thresh,
-                self.cost.kind, self.cost.index, self.weights, self.state, self.last_reward, self.counters,
-                self.first_refused, admitted_rec=rec, worst_rec=worst, member_refusals=self.member_refusals,
-                status=self.status), rec, worst
+        kernel = safe_kernels.cacla_safe_ensemble_run if self.ensemble else safe_kernels.cacla_safe_run
 
-        def launch(c, t, noise):
+        def launch(c, t, noise):   # -> the chunk's rewards and admit flags, and behind them an ensemble's worst costs
             rec = torch.empty((self.A, c), dtype=torch.int32, device=self.device)
-            return safe_kernels.cacla_safe_run(
-                self.p, c, t, self.gamma, self.alpha, noise, self.gated, self.sim, self.sim_thresh, self.real_thresh,
-                self.cost.kind, self.cost.index, self.weights, self.state, self.last_reward, self.counters,
-                self.first_refused, admitted_rec=rec, status=self.status), rec
+            worst = torch.empty((self.A, c), dtype=torch.float64, device=self.device) if self.ensemble else None
+            records = dict(worst_rec=worst, member_refusals=self.member_refusals) if self.ensemble else {}
+            rewards = kernel(self.p, c, t, self.gamma, self.alpha, noise, self.gated, self.sim, self.sim_thresh,
+                             self.real_thresh, self.cost.kind, self.cost.index, self.weights, self.state,
+                             self.last_reward, self.counters, self.first_refused, admitted_rec=rec,
+                             status=self.status, **records)
+            return (rewards, rec, worst) if self.ensemble else (rewards, rec)
 
-        if self.ensemble:
-            rewards, admitted, self.worst_cost = run_chunks(self.device, self.A, self.p.m, sizes, draw, launch_ensemble)
-        else:
-            rewards, admitted = run_chunks(self.device, self.A, self.p.m, sizes, draw, launch)
+        rewards, admitted, *worst = run_chunks(self.device, self.A, self.p.m, sizes, draw, launch)
+        self.worst_cost = worst[0] if self.ensemble else None
         return rewards, admitted.astype(bool)
 
 

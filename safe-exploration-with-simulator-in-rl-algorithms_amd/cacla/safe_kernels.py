@@ -1,6 +1,7 @@
-"""The checked wrapper of sw_cacla_safe_run_f64 (include/swimmer_hip.h): device tensors in, ONE foreign call.  It
-lives here, next to the classes that use it, and goes through the argument checks of swimmer_amd.kernels: dtype, exact
-shape, contiguity and the device of the call's first required tensor, a SwimmerHipError that names the parameter."""
+"""The checked wrappers of sw_cacla_safe_run_f64 and sw_cacla_safe_ensemble_run_f64 (include/swimmer_hip.h): device
+tensors in, ONE foreign call each.  They live here, next to the classes that use them, and go through the argument
+checks of swimmer_amd.kernels: dtype, exact shape, contiguity and the device of the call's first required tensor, a
+SwimmerHipError that names the parameter."""
 import ctypes
 
 import torch
@@ -9,6 +10,27 @@ from ..kernels import _gpu, _Min, _opt, _out, _tensor, cacla_net_doubles
 from .._lib import STATUS_PARAM, SwParams, check, load, ptr, require_gpu, stream_ptr  # noqa: F401
 
 _I32 = torch.int32
+
+
+def _gated_args(p, n_iter, gamma, alpha, noise, gated, sims, sims_name, sims_shape, sim_thresh, real_thresh, weights,
+                state, last_reward, counters, first_refused, admitted_rec):
+    """The tensor checks both wrappers share, in the order the library takes the arguments; the simulators' array is
+    [A, *sims_shape].  -> (the call's device, A)."""
+    on = _gpu(gamma, "gamma", 1)
+    A = _tensor(gamma, "gamma", (_Min(1),), on).shape[0]
+    _tensor(alpha, "alpha", (A,), on)
+    _tensor(noise, "noise", (A, n_iter, p.m), on)
+    _tensor(gated, "gated", (A,), on, _I32)
+    _tensor(sims, sims_name, (A,) + sims_shape, on)
+    _tensor(sim_thresh, "sim_thresh", (A,), on)
+    _tensor(real_thresh, "real_thresh", (A,), on)
+    _tensor(weights, "weights", (A, p.n, cacla_net_doubles(p.n)), on)
+    _tensor(state, "state", (A, p.d), on)
+    _tensor(last_reward, "last_reward", (A,), on)
+    _tensor(counters, "counters", (A, 3), on, _I32)
+    _tensor(first_refused, "first_refused", (A,), on, _I32)
+    _opt(admitted_rec, "admitted_rec", (A, n_iter), on, _I32)
+    return on, A
 
 
 def cacla_safe_run(p: SwParams, n_iter: int, t_begin: int, gamma, alpha, noise, gated, sim, sim_thresh, real_thresh,
@@ -22,20 +44,8 @@ def cacla_safe_run(p: SwParams, n_iter: int, t_begin: int, gamma, alpha, noise, 
     written / accumulated when given.  t_begin: the steps of the run already taken (first_refused counts from the
     run's start).  Returns `rewards` [A, n_iter]: the last admitted step's reward, NaN before the first admission."""
     require_gpu()
-    on = _gpu(gamma, "gamma", 1)
-    A = _tensor(gamma, "gamma", (_Min(1),), on).shape[0]
-    _tensor(alpha, "alpha", (A,), on)
-    _tensor(noise, "noise", (A, n_iter, p.m), on)
-    _tensor(gated, "gated", (A,), on, _I32)
-    _tensor(sim, "sim", (A, 3), on)
-    _tensor(sim_thresh, "sim_thresh", (A,), on)
-    _tensor(real_thresh, "real_thresh", (A,), on)
-    _tensor(weights, "weights", (A, p.n, cacla_net_doubles(p.n)), on)
-    _tensor(state, "state", (A, p.d), on)
-    _tensor(last_reward, "last_reward", (A,), on)
-    _tensor(counters, "counters", (A, 3), on, _I32)
-    _tensor(first_refused, "first_refused", (A,), on, _I32)
-    _opt(admitted_rec, "admitted_rec", (A, n_iter), on, _I32)
+    on, A = _gated_args(p, n_iter, gamma, alpha, noise, gated, sim, "sim", (3,), sim_thresh, real_thresh, weights,
+                        state, last_reward, counters, first_refused, admitted_rec)
     _opt(status, "status", (A,), on, _I32)
     rewards = _out(rewards, "rewards", (A, n_iter), on)
     check(load().sw_cacla_safe_run_f64(ctypes.byref(p), A, int(n_iter), int(t_begin), ptr(gamma), ptr(alpha),
@@ -57,20 +67,9 @@ def cacla_safe_ensemble_run(p: SwParams, n_iter: int, t_begin: int, gamma, alpha
     ungated agent) and member_refusals int32 [A, E] (zero before a run) accumulates the steps at which each member's
     own cost was not <= sim_thresh.  Returns `rewards` [A, n_iter]."""
     require_gpu()
-    on = _gpu(gamma, "gamma", 1)
-    A = _tensor(gamma, "gamma", (_Min(1),), on).shape[0]
-    _tensor(alpha, "alpha", (A,), on)
-    _tensor(noise, "noise", (A, n_iter, p.m), on)
-    _tensor(gated, "gated", (A,), on, _I32)
-    E = _tensor(sims, "sims", (A, _Min(1), 3), on).shape[1]
-    _tensor(sim_thresh, "sim_thresh", (A,), on)
-    _tensor(real_thresh, "real_thresh", (A,), on)
-    _tensor(weights, "weights", (A, p.n, cacla_net_doubles(p.n)), on)
-    _tensor(state, "state", (A, p.d), on)
-    _tensor(last_reward, "last_reward", (A,), on)
-    _tensor(counters, "counters", (A, 3), on, _I32)
-    _tensor(first_refused, "first_refused", (A,), on, _I32)
-    _opt(admitted_rec, "admitted_rec", (A, n_iter), on, _I32)
+    on, A = _gated_args(p, n_iter, gamma, alpha, noise, gated, sims, "sims", (_Min(1), 3), sim_thresh, real_thresh,
+                        weights, state, last_reward, counters, first_refused, admitted_rec)
+    E = sims.shape[1]
     _opt(worst_rec, "worst_rec", (A, n_iter), on)
     _opt(member_refusals, "member_refusals", (A, E), on, _I32)
     _opt(status, "status", (A,), on, _I32)

@@ -241,8 +241,7 @@ int sw_safe_rollouts_f64(const sw_params *real, const sw_params *sim, int64_t n_
     if (rc) return rc;
     if (real->n != sim->n) return SW_ERR_SEGMENTS;
     if (n_roll < 0 || H < 0) return SW_ERR_SIZE;
-    if (cost_kind != SW_COST_ABS_OBS && cost_kind != SW_COST_MAX_ABS_THETADOT) return SW_ERR_SIZE;
-    if (cost_kind == SW_COST_ABS_OBS && (cost_index < 0 || cost_index >= 2 * real->n + 2)) return SW_ERR_SIZE;
+    if ((rc = check_cost(real, cost_kind, cost_index)) != SW_OK) return rc;
     if (!(sim_thresh == sim_thresh) || !(real_thresh == real_thresh)) return SW_ERR_PARAM;
     if (n_roll == 0) return SW_OK;
     if (!policies || !returns) return SW_ERR_NULL;
@@ -382,8 +381,7 @@ int sw_safe_ars_rollouts_multi_f64(const sw_params *real, int64_t n_agent, int64
     if (rc) return rc;
     const MultiPlan m = plan_multi(real, &FormLaunchers::safe_ars_multi, n_agent, n_dir, H, cost_trace != nullptr);
     if (!m.in_range) return SW_ERR_SIZE;
-    if (cost_kind != SW_COST_ABS_OBS && cost_kind != SW_COST_MAX_ABS_THETADOT) return SW_ERR_SIZE;
-    if (cost_kind == SW_COST_ABS_OBS && (cost_index < 0 || cost_index >= 2 * real->n + 2)) return SW_ERR_SIZE;
+    if ((rc = check_cost(real, cost_kind, cost_index)) != SW_OK) return rc;
     if (!policy || !deltas || !gated || !sim || !sim_thresh || !real_thresh || !returns) return SW_ERR_NULL;
     if (!m.fits) return SW_ERR_SIZE;
     const SafeArsMultiArgs a{policy,  deltas,     gated,    sim,           sim_thresh, real_thresh,

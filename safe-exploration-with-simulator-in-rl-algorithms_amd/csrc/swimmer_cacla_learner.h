@@ -1,8 +1,9 @@
 // swimmer_cacla_learner.h -- the CACLA learner on the swimmer (cacla/cacla_agent.py:135-199), ONE WAVE PER AGENT: what
-// cacla_kernel (swimmer_cacla.hip), cacla_safe_kernel (swimmer_cacla_safe.hip) and cacla_ensemble_kernel
-// (swimmer_cacla_ensemble.hip) all run.  The kernels call the pieces below in the same order, so an ungated agent of
-// sw_cacla_safe_run_f64 or sw_cacla_safe_ensemble_run_f64 has the bits of sw_cacla_run_f64(train = 1) by construction
-// (tests/test_cacla_safe_gpu.py and tests/test_cacla_ensemble_gpu.py hold them to it at every n).
+// cacla_kernel<N, TRAIN> (swimmer_cacla.hip) and cacla::gated_kernel<N, ENSEMBLE> (swimmer_cacla_gated.h, instantiated
+// by swimmer_cacla_safe.hip and swimmer_cacla_ensemble.hip) run.  The kernels call the pieces below in the same order,
+// so an ungated agent of sw_cacla_safe_run_f64 or sw_cacla_safe_ensemble_run_f64 has the bits of
+// sw_cacla_run_f64(train = 1) by construction (tests/test_cacla_safe_gpu.py and tests/test_cacla_ensemble_gpu.py hold
+// them to it at every n).
 //
 // One step (cacla_agent.py:170-193): actor forward, Gaussian action, physics step, critic at the new and at the old
 // state, SGD step on the critic, SGD step on the actors when the temporal difference is positive.  No clipping, no
@@ -33,7 +34,11 @@
 // Free functions over arrays that stay plain locals of the kernel, on purpose: a struct that owns W1, b1, W2 as
 // members costs 26 .. 78 more registers per lane at n >= 6 (the compiler stops keeping the weights where it does now).
 // Adding a step's noise to the actors' outputs stays a line of each kernel for the same reason: as a function here it
-// costs cacla_safe_kernel<8> four registers, one allocation granule.
+// costs the single-simulator gated kernel at n = 8 four registers, one allocation granule.  The run loop is a
+// __global__ template for the same reason again: as a __device__ __forceinline__ function behind two thin kernels, its
+// arguments by reference or by value, all 14 gated kernels change -- 26 .. 32 more AGPRs at n = 6, 7, 8 (one simulator,
+// n = 8: 134 -> 162), 219 -> 242 VGPRs with one simulator at n = 5, 255 VGPRs + 2 AGPRs with an ensemble at n = 5, up to
+// 160 more instructions.
 #pragma once
 #include "swimmer_launch.h"
 

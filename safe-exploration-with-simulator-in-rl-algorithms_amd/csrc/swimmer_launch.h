@@ -94,14 +94,16 @@
 //                              (a hidden unit per lane, two from n = 6), the physics redundantly in every lane, the
 //                              n + 1 network outputs of a step summed through LDS in a fixed order and handed out
 //                              with v_readlane; instruction-issue bound like the latency forms
+//   swimmer_cacla_gated.h      the gated run loop of the two files below, ONE kernel body: cacla::gated_kernel<N, ENSEMBLE>,
+//                              with their argument check and launch (cacla::gated_run<ENSEMBLE>)
 //   swimmer_cacla_safe.hip (a translation unit of its own)
-//   cacla_safe_kernel<N>       sw_cacla_safe_run_f64: the same learner behind a per-step simulator gate, per agent gated
-//                              or not: cacla_kernel's learner in its order (an ungated agent has its bits), plus the
+//   cacla::gated_kernel<N, false>  sw_cacla_safe_run_f64: the same learner behind a per-step simulator gate, per agent
+//                              gated or not: cacla_kernel's learner in its order (an ungated agent has its bits), plus the
 //                              simulator's look-ahead step and the cost redundantly in every lane, the admit decision
 //                              taken from the first lane into a scalar register, the real step and the update behind
 //                              a uniform branch; reward entry and admit flag staged per lane, stored once per block
 //   swimmer_cacla_ensemble.hip (a translation unit of its own)
-//   cacla_ensemble_kernel<N>   sw_cacla_safe_ensemble_run_f64: cacla_safe_kernel's run loop with the look-ahead in an
+//   cacla::gated_kernel<N, true>  sw_cacla_safe_ensemble_run_f64: the same run loop with the look-ahead in an
 //                              ENSEMBLE of up to 64 simulators: lane L holds the constants of member L % n_member in
 //                              VGPRs, so the same instructions look ahead in every member; the admit decision is a wave
 //                              ballot over every lane's verdict; optionally the worst member cost per step (a wave
@@ -348,6 +350,15 @@ int check_params(const sw_params *p)
 int launch_status()
 {
     return hipGetLastError() == hipSuccess ? SW_OK : SW_ERR_LAUNCH;
+}
+
+// The state cost of the safe-exploration entry points (SW_COST_*): a known kind, and for |obs[index]| an index inside
+// the real model's observation.
+int check_cost(const sw_params *real, int32_t cost_kind, int32_t cost_index)
+{
+    if (cost_kind != SW_COST_ABS_OBS && cost_kind != SW_COST_MAX_ABS_THETADOT) return SW_ERR_SIZE;
+    if (cost_kind == SW_COST_ABS_OBS && (cost_index < 0 || cost_index >= 2 * real->n + 2)) return SW_ERR_SIZE;
+    return SW_OK;
 }
 
 // ---- dispatch on the segment count -------------------------------------------------

@@ -123,8 +123,7 @@ int sw_safe_ars_rollouts_ensemble_f64(const sw_params *real, int64_t n_agent, in
     // the size rule of the multi-agent launches: grid.y = agent, rollouts indexed like a single launch's
     if (n_agent < 1 || n_agent > 65535 || n_dir < 1 || n_dir > ((int64_t)1 << 23) || H < 0) return SW_ERR_SIZE;
     if (n_member < 1 || n_member > kWave) return SW_ERR_SIZE;   // the members ride in one wave's lanes
-    if (cost_kind != SW_COST_ABS_OBS && cost_kind != SW_COST_MAX_ABS_THETADOT) return SW_ERR_SIZE;
-    if (cost_kind == SW_COST_ABS_OBS && (cost_index < 0 || cost_index >= 2 * real->n + 2)) return SW_ERR_SIZE;
+    if ((rc = check_cost(real, cost_kind, cost_index)) != SW_OK) return rc;
     if (!policy || !deltas || !gated || !sims || !sim_thresh || !real_thresh || !returns) return SW_ERR_NULL;
     int32_t log2_group = 0;
     while ((1 << log2_group) < n_member) ++log2_group;

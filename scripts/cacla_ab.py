@@ -1,5 +1,6 @@
-"""Same-box A/B of the two CACLA swimmer kernels (sw_cacla_run_f64, sw_cacla_safe_run_f64) between two builds of
-libswimmer_hip.so: are the results the same bits, and is the kernel time the same.
+"""Same-box A/B of the three CACLA swimmer kernels (sw_cacla_run_f64, sw_cacla_safe_run_f64,
+sw_cacla_safe_ensemble_run_f64) between two builds of libswimmer_hip.so: are the results the same bits, and is the
+kernel time the same.
 
     python scripts/cacla_ab.py OLD.so NEW.so [--rounds R] [--timeout SECONDS] [--log FILE]
 
@@ -7,13 +8,16 @@ Per round and library one fresh child process (scripts/ab_common.py has the prot
 floor and the exit codes).  A child
 
   * runs fixed-seed cases at n = 2 .. 8, 6 agents x 150 steps (two full 64-step noise blocks and a partial one): the
-    plain kernel with train on and off, and the gated kernel with gated = [1, 0, 1, 1, 0, 1] behind simulators that
-    refuse some steps and admit others (checked), and saves rewards, weights, state, counters, admit records and
-    status to an .npz in a temporary directory;
+    plain kernel with train on and off, the gated kernel with gated = [1, 0, 1, 1, 0, 1] behind simulators that
+    refuse some steps and admit others (checked), and the ensemble-gated kernel with the same agents behind
+    E = 1, 5 and 64 members spread around that simulator (checked likewise), once with the worst-cost record and the
+    members' refusal counts and once without either; it saves rewards, weights, state, counters, admit records,
+    status, the ensembles and their records to an .npz in a temporary directory;
   * times the kernels alone, HIP events around one launch with the noise already on the device (as
     scripts/cacla_probe.py (c)): the reference's grid of 960 agents at n = 3 x 2048 steps and at n = 8 x 512 steps,
-    the gated kernel with every agent gated and a gate that admits every step (look-ahead, real step and update at
-    every step).  Median of 5 after two warm-up launches, with min and max.
+    the gated kernels with every agent gated and a gate that admits every step (look-ahead, real step and update at
+    every step), the ensemble-gated one with E = 1 and E = 64 copies of the simulator and both records.  Median of 5
+    after two warm-up launches, with min and max.
 
 The parent compares the arrays bit for bit and the timings against the spread of OLD's medians over the rounds."""
 import json
@@ -30,6 +34,8 @@ REPS, WARM = 5, 2
 SIM = (1.02, 0.97, 10.3)
 CASE_AGENTS, CASE_STEPS = 6, 150
 CASE_GATED = [1, 0, 1, 1, 0, 1]
+CASE_MEMBERS, MEMBER_SPREAD = (1, 5, 64), 0.01   # ensemble sizes of the cases; members within 1 % of SIM
+TIMED_MEMBERS = (1, 64)
 SHAPES = ((3, 2048), (8, 512))          # (n, steps) of the timed launches; 960 agents each
 
 
@@ -39,6 +45,13 @@ def grid():
            for a in (0.1, 0.03, 0.01, 0.003, 0.001, 0.0003, 0.0001, 0.00003) for s in (1, 0.1, 0.001, 0.0001)
            for _ in range(3)]
     return tuple(np.array([x[i] for x in per], dtype=np.float64) for i in range(3))
+
+
+def members(A, E):
+    """[A, E, 3] simulators for the cases: member 0 is SIM, the others lie within MEMBER_SPREAD of it."""
+    spread = np.random.RandomState(E).uniform(-MEMBER_SPREAD, MEMBER_SPREAD, (A, E, 3))
+    spread[:, 0] = 0.0
+    return np.asarray(SIM) * (1.0 + spread)
 
 
 def child(out_dir):
@@ -84,6 +97,28 @@ def child(out_dir):
               f"{arrays[f'gated_n{n}_counters'][:, 2].tolist()}", flush=True)
         for a in range(A):
             assert (0 < adm[a] < steps) if CASE_GATED[a] else adm[a] == steps, (n, a, adm[a])
+        for E in CASE_MEMBERS:
+            sims = members(A, E)
+            arrays[f"ens_n{n}_E{E}_sims"] = sims
+            for records in (True, False):
+                w, s, (last, counters, first) = w0.clone(), s0.clone(), gate_state(A)
+                rec = torch.empty((A, steps), dtype=torch.int32, device=DEV)
+                status = torch.zeros(A, dtype=torch.int32, device=DEV)
+                worst = torch.empty((A, steps), dtype=torch.float64, device=DEV) if records else None
+                refusals = torch.zeros((A, E), dtype=torch.int32, device=DEV) if records else None
+                r = safe_kernels.cacla_safe_ensemble_run(
+                    p, steps, 0, gam, alp, noise, i32(CASE_GATED), f64(sims), f64([0.05] * A), f64([0.04] * A),
+                    max_thetadot, 0, w, s, last, counters, first, admitted_rec=rec, worst_rec=worst,
+                    member_refusals=refusals, status=status)
+                out = [("rewards", r), ("weights", w), ("state", s), ("last_reward", last), ("counters", counters),
+                       ("first_refused", first), ("admitted_rec", rec), ("status", status)]
+                out += [("worst_rec", worst), ("member_refusals", refusals)] if records else []
+                for key, v in out:
+                    arrays[f"ens_n{n}_E{E}_records{int(records)}_{key}"] = v.cpu().numpy()
+                adm = arrays[f"ens_n{n}_E{E}_records{int(records)}_counters"][:, 0]
+                for a in range(A):
+                    assert (0 < adm[a] < steps) if CASE_GATED[a] else adm[a] == steps, (n, E, a, adm[a])
+            print(f"  cases n = {n}, E = {E}: admitted steps per agent {adm.tolist()}", flush=True)
     np.savez(os.path.join(out_dir, "cases.npz"), **arrays)
 
     # ---- kernel-only time
@@ -125,7 +160,23 @@ def child(out_dir):
             safe_kernels.cacla_safe_run(p, steps, 0, gam, alp, noise, gated, sim, sim_thr, real_thr, max_thetadot, 0,
                                         w, s, last, counters, first, rewards=rewards, admitted_rec=rec)
 
-        for name, launch in (("sw_cacla_run_f64", plain), ("sw_cacla_safe_run_f64", gate)):
+        def ensemble_gate(E):
+            sims = f64(np.tile(SIM, (A, E, 1)))
+            worst = torch.empty(A, steps, dtype=torch.float64, device=DEV)
+
+            def launch(fresh):
+                if fresh is None:
+                    refusals = torch.zeros((A, E), dtype=torch.int32, device=DEV)
+                    return (w0.clone(), s0.clone()) + gate_state(A) + (refusals,)
+                w, s, last, counters, first, refusals = fresh
+                safe_kernels.cacla_safe_ensemble_run(p, steps, 0, gam, alp, noise, gated, sims, sim_thr, real_thr,
+                                                     max_thetadot, 0, w, s, last, counters, first, rewards=rewards,
+                                                     admitted_rec=rec, worst_rec=worst, member_refusals=refusals)
+            return launch
+
+        rows = [("sw_cacla_run_f64", plain), ("sw_cacla_safe_run_f64", gate)]
+        rows += [(f"sw_cacla_safe_ensemble_run_f64 E={E}", ensemble_gate(E)) for E in TIMED_MEMBERS]
+        for name, launch in rows:
             times[f"{name} n={n} {A}x{steps}"] = timed(launch)
     with open(os.path.join(out_dir, "times.json"), "w") as f:
         json.dump(times, f)
